@@ -30,6 +30,16 @@ Extra objects on the JSON line:
                whole-step rates (executed FLOP and the reference's own arithmetic over the measured step time).
   cpu_baseline the oracle (CPU restatement of the reference path) timed on this box's host cores, bounded sample
                (cifar256 and bedroom256; null for the other configs).
+
+--dump-outputs DIR writes what the timed run computed -- the arrays its caller receives -- as DIR/<name>.npy (float32 / float64,
+64 MB at most), so that two builds can be compared output for output on identical seeded inputs:
+  cifar256, bedroom256  losses (per executed timestep), scores (every pruned group's channel scores, concatenated),
+                        pruned_channels + pruned_per_group (the masks), params + grads of the pruned model (same positions)
+  c4_finetune           loss (last step), params + ema after the last step
+  ddim                  x (the sample after the last DDIM step)
+  ldm                   losses, grads (the accumulated importance gradients)
+An array of more than 4194304 elements is replaced by a fixed sample of that many, at positions drawn from a seeded generator
+(the same positions for every array of the same length).
 """
 import argparse
 import importlib
@@ -38,6 +48,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -53,10 +64,45 @@ FLOP_BEDROOM_IMG_STEP = 1.491e12
 FLOP_PRUNED_CIFAR_IMG_STEP = 20.6e9
 FLOP_PRUNED_CIFAR_FWD = 6.87e9
 FLOP_LDM_FWD, FLOP_LDM_FWD_BWD = 208.4e9, 625e9
+DUMP_SAMPLE = 4 << 20            # --dump-outputs: elements kept of a larger array (16 MB in float32)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def pkg(sub):
     return importlib.import_module('diff-pruning_amd.' + sub)
+
+
+def _sample(flat):
+    """`flat` (1-D) itself up to DUMP_SAMPLE elements, else DUMP_SAMPLE of them at sorted positions from a generator of fixed
+    seed: arrays of equal length (params and their grads) are sampled at the same positions, in every run and every build."""
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat
+    idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def _model_outputs(model):
+    """params + grads of `model`, flattened in parameter order (a missing grad counts as zeros) and sampled alike."""
+    ps = list(model.parameters())
+    params = torch.cat([p.detach().reshape(-1) for p in ps])
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in ps])
+    return {'params': _sample(params), 'grads': _sample(grads)}
+
+
+def dump_outputs(outputs, out_dir):
+    """Write {name: tensor / sequence} as out_dir/<name>.npy: float32 stays float32, everything else becomes float64."""
+    arrays = {}
+    for name, v in outputs.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrays[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte bound' % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def cpu_baseline(config, steps=8):
@@ -204,6 +250,7 @@ class SweepWorkload:
         pr = sweep.prune_model(self.model, 0.3)                          # scoring + mask selection + slicing
         self.env.barrier()
         t_total = time.perf_counter() - t0
+        self.last = (res, pr)
         return dict(units=self.env.world * self.B * res['steps'], steps_done=res['steps'], t_total=t_total, t_steps=tm['sweep_s'],
                     extra={'sweep_only_images_per_s': self.env.world * self.B * res['steps'] / tm['sweep_s'],
                            'tail_ms': (t_total - tm['sweep_s']) * 1e3,
@@ -220,6 +267,16 @@ class SweepWorkload:
                            'diff_pruning_threshold': self.thr,
                            'pruned_groups': len(pr.records), 'params_after': sum(p.numel() for p in self.model.parameters()),
                            'loss_first_last': [res['losses'][0], res['losses'][-1]]})
+
+    def outputs(self):
+        res, pr = self.last
+        out = {'losses': res['losses'],
+               'scores': torch.cat([torch.as_tensor(score).double().cpu().reshape(-1) for _, _, score, _ in pr.records]
+                                   + [torch.zeros(0, dtype=torch.float64)]),
+               'pruned_channels': [int(i) for _, _, _, idxs in pr.records for i in idxs],
+               'pruned_per_group': [len(idxs) for _, _, _, idxs in pr.records]}
+        out.update(_model_outputs(self.model))
+        return out
 
     def workload(self, K):
         return ('%s, batch %d/GPU, %s sweep t=0..%d + grad all-reduce + |w*g| scoring + mask selection + slicing (ratio 0.3)'
@@ -274,6 +331,7 @@ class FinetuneWorkload:
         t_enq = time.perf_counter() - t0
         self.env.barrier()
         t_total = time.perf_counter() - t0
+        self.last_loss = loss
         return dict(units=self.env.world * self.B * K, steps_done=K, t_total=t_total, t_steps=t_total,
                     extra={'host_enqueue_ms_per_step': t_enq / K * 1e3,
                            'kernel_launches_per_step': ((self.ft._cap['call'].info.get('kernels', 0) if self.ft._cap else 0)
@@ -281,6 +339,12 @@ class FinetuneWorkload:
                            'step_replayed_natively': self.ft._cap is not None,
                            'replay_info': dict(self.ft._cap['call'].info) if self.ft._cap else None, 'dropout': 0.1,
                            'params': sum(p.numel() for p in self.model.parameters()), 'last_local_loss': float(loss)})
+
+    def outputs(self):
+        out = {'loss': self.last_loss.reshape(-1), 'params': _sample(self.ft.flat_p)}
+        if self.ft.ema is not None:
+            out['ema'] = _sample(self.ft.ema)
+        return out
 
     def workload(self, K):
         return ('pruned ddpm-cifar10 UNet (19.85M params) finetune step (ddpm_train.py), batch %d/GPU, dropout 0.1, '
@@ -343,6 +407,7 @@ class DdimWorkload:
         t_enq = time.perf_counter() - t0
         self.env.barrier()
         t_total = time.perf_counter() - t0
+        self.last_x = x
         replayed = type(self.fwd).__name__ == '_CapturedForward'
         info = dict(self.fwd.call.info) if replayed else {}
         self.fwd.close()
@@ -352,6 +417,9 @@ class DdimWorkload:
                            else (lib.dp_launch_count() - launches0) / K,
                            'forward_replayed_natively': replayed, 'replay_nodes': info.get('nodes'),
                            'finite': bool(torch.isfinite(x).all())})
+
+    def outputs(self):
+        return {'x': _sample(self.last_x.reshape(-1))}
 
     def workload(self, K):
         return 'pruned ddpm-cifar10 UNet (19.85M params) DDIM sampling loop (ddpm_sample.py), batch %d/GPU, eta 0' % self.B
@@ -402,11 +470,15 @@ class LdmWorkload:
         res = self._pass(K, 2)
         self.env.barrier()
         t_total = time.perf_counter() - t0
+        self.last = res
         return dict(units=self.n * res['steps'], steps_done=res['steps'], t_total=t_total, t_steps=t_total,
                     extra={'kernel_launches_per_step': (lib.dp_launch_count() - launches0) / max(res['steps'], 1),
                            'latents_this_rank': res['shard'][1] - res['shard'][0], 'accumulated': res['accumulated'],
                            'loss_first_last': [res['losses'][0], res['losses'][-1]],
                            'params': sum(p.numel() for p in self.model.parameters())})
+
+    def outputs(self):
+        return {'losses': self.last['losses'], 'grads': _sample(self.last['flat_grads'])}
 
     def workload(self, K):
         return ('LDM cin256-v2 UNet (400.9M params, seeded weights) importance pass (prune_ldm.py): %d latents 3x64x64 per step '
@@ -534,12 +606,16 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--graph', action='store_true', help='replay the timestep from a captured hipGraph (sweep configs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what they computed as DIR/<name>.npy (see the module docstring)')
     ap.add_argument('--backend', default='nccl', help="process-group backend; 'gloo' with ranks sharing a GPU is a logic check of the N > 1 path on a 1-GPU box, not a measurement")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = DEFAULT_STEPS[args.config][0]
     if args.warmup is None:
         args.warmup = DEFAULT_STEPS[args.config][1]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         _self_launch(args)
@@ -579,6 +655,9 @@ def main():
     wl.warmup(args.warmup)
     env.barrier()
     r = wl.run(args.steps)                        # starts its clock right after the barrier, ends it behind another one
+    dumped = None
+    if rank == 0 and args.dump_outputs:           # before the roofline pass, which may step the same model again
+        dumped = dump_outputs(wl.outputs(), args.dump_outputs)
     tt = torch.tensor([r['t_total'], r['t_steps']], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -606,6 +685,8 @@ def main():
         out = {'metric': wl.metric, 'value': r['units'] / t_total, 'unit': wl.unit, 'n_gpus': world, 'steps': args.steps,
                'warmup': args.warmup, 'ms_per_step': step_seconds * 1e3, 'higher_is_better': True, 'scaling': wl.scaling,
                'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'config': cfg, 'roofline': roof, 'cpu_baseline': cpu}
+        if dumped is not None:
+            out['dumped_outputs'] = dict(dir=args.dump_outputs, arrays=dumped)
         if args.backend != 'nccl':
             out['config']['backend'] = args.backend + ' (logic check, not a measurement)'
         print(json.dumps(out), flush=True)

@@ -95,7 +95,8 @@ _SIGNALLED = []
 
 def pytest_terminal_summary(terminalreporter):
     for node, rc, tail in _SIGNALLED:
-        terminalreporter.write_line('[dp-test] CHILD KILLED BY SIGNAL %d (re-run once): %s' % (-rc, node))
+        terminalreporter.write_line('[dp-test] CHILD %s (session stopped): %s'
+                                    % ('KILLED BY SIGNAL %d' % -rc if isinstance(rc, int) else str(rc).upper(), node))
         terminalreporter.write_line(tail)
 
 
@@ -144,13 +145,13 @@ def isolated(timeout=900, params=()):
             request = kwargs.pop('request')
             tmp = request.getfixturevalue('tmp_path')
             rc, tail, rep = run_isolated(request.node.nodeid, tmp, timeout)
-            if isinstance(rc, int) and rc < 0:
-                # killed by a signal (SIGABRT -6, SIGSEGV -11, SIGKILL -9): keep the evidence -- log line, report entry, terminal
-                # summary -- and run the node ONCE more, so that a crash that depends on the lease's timing is recorded as such
-                # (first attempt died, second passed / died again) instead of ending the suite with the other rows unrun
+            if not isinstance(rc, int) or rc < 0:
+                # killed by a signal (SIGABRT -6, SIGSEGV -11, SIGKILL -9) or timed out: the device may be faulted or hung, so
+                # nothing else is started on it -- keep the evidence (log line, report entry, terminal summary), fail this
+                # node and stop the session after it.  The node is not run again.
                 _SIGNALLED.append((request.node.nodeid, rc, tail[-1500:]))
                 _REPORT.setdefault('harness/child_signals', []).append(dict(node=request.node.nodeid, rc=rc, tail=tail[-1500:]))
-                rc, tail, rep = run_isolated(request.node.nodeid, tmp, timeout)
+                request.session.shouldstop = 'child interpreter for %s ended with %s' % (request.node.nodeid, rc)
             _REPORT.update(rep)
             assert rc == 0, 'child interpreter for %s ended with %s\n%s' % (request.node.nodeid, rc, tail)
 
