@@ -259,3 +259,93 @@ def write_lmdb(path, items, psize=4096, max_leaf_keys=None):
         for pg in range(2, next_pg[0]):
             f.write(pages.get(pg, b'\0' * psize))
 
+
+
+# ---- fp64 references on structured subsets (tests/test_launch_parity_gpu.py) ---------------------------------------------
+# Only where the kernels have edges: whole images for the per-image operations (first, last, and the two images on either side of
+# the first 128-pixel tile boundary -- at 4 x 4 and 8 x 8 a pixel tile spans several images), and for the weight gradients the
+# first and the last 64-row tile x the first and the last 32-column tile, always reduced over EVERY pixel (every split-K slice).
+def edge_images(N, hw):
+    """Image indices whose outputs the parity tests compare for an [N, C, H, W] result with hw = H * W pixels per image."""
+    return sorted({0, min(N - 1, 127 // hw), min(N - 1, 128 // hw), N - 1})
+
+
+def edge_tiles(n, t):
+    """Indices of the first and of the last t-wide tile of range(n) (the last one may be a partial tail tile)."""
+    last = (n - 1) // t * t
+    return sorted(set(range(min(t, n))) | set(range(last, n)))
+
+
+def spec_pads(spec):
+    """(top, bottom, left, right) zero padding of an ops.ConvSpec convolution applied to its (upsampled) input."""
+    if spec.keep:                                  # ConvSpec.same: output size = input size
+        return spec.pad_h, spec.kh - 1 - spec.pad_h, spec.pad_w, spec.kw - 1 - spec.pad_w
+    if spec.sym or spec.stride == 1:
+        return spec.pad_h, spec.pad_h, spec.pad_w, spec.pad_w
+    if spec.pad == 0:                              # stride 2, pad 0: the asymmetric (0, 1, 0, 1) pad
+        return 0, 1, 0, 1
+    return spec.pad, spec.pad, spec.pad, spec.pad
+
+
+def ref_conv_input(x, spec, ups=None):
+    """x (fp64, CPU) upsampled (nearest x2 when the spec fuses it) and zero-padded: conv(spec) = F.conv2d(result, w, stride)."""
+    import torch.nn.functional as F
+    if spec.ups if ups is None else ups:
+        x = x.repeat_interleave(2, 2).repeat_interleave(2, 3)
+    pt, pb, pl, pr = spec_pads(spec)
+    return F.pad(x, (pl, pr, pt, pb))
+
+
+def ref_conv_fwd(x, w, spec):
+    import torch.nn.functional as F
+    return F.conv2d(ref_conv_input(x, spec), w, stride=spec.stride)
+
+
+def ref_conv_dgrad(dy, w, spec, in_hw):
+    """Gradient w.r.t. the virtual (post-upsample) input of size in_hw, as ops.conv_dgrad defines it."""
+    import torch.nn.functional as F
+    xv = torch.zeros((dy.shape[0], w.shape[1]) + tuple(in_hw), dtype=torch.float64, requires_grad=True)
+    y = F.conv2d(ref_conv_input(xv, spec, ups=0), w, stride=spec.stride)
+    assert y.shape == dy.shape, (tuple(y.shape), tuple(dy.shape))
+    return torch.autograd.grad(y, xv, dy)[0]
+
+
+def ref_conv_wgrad(dy, x, spec, kh, kw, max_elems=1 << 25):
+    """sum over every image and pixel of dy (x) im2col(x): [R, K, kh, kw] for dy [N, R, Ho, Wo] (the selected output rows) and
+    x [N, K, Hs, Ws] (the selected input channels); tensors may live on any device, images go to the host in chunks."""
+    import torch.nn.functional as F
+    N, R = dy.shape[:2]
+    K = x.shape[1]
+    per = max(1, K * kh * kw * dy.shape[2] * dy.shape[3])
+    step = max(1, max_elems // per)
+    acc = torch.zeros(R, K * kh * kw, dtype=torch.float64)
+    for n0 in range(0, N, step):
+        xc = ref_conv_input(x[n0:n0 + step].double().cpu(), spec)
+        unf = F.unfold(xc, (kh, kw), stride=spec.stride)                      # [n, K*kh*kw, Ho*Wo]
+        d = dy[n0:n0 + step].double().cpu().reshape(unf.shape[0], R, -1)
+        assert d.shape[2] == unf.shape[2]
+        acc += torch.einsum('nrl,nkl->rk', d, unf)
+    return acc.view(R, K, kh, kw)
+
+
+def ref_groupnorm(x, gamma, beta, G, eps, silu):
+    """silu?(group_norm(x)) in fp64 with per-image affine parameters gamma / beta [N, C] (or [C])."""
+    import torch.nn.functional as F
+    N, Cc = x.shape[:2]
+    xg = x.reshape(N, G, -1)
+    mean = xg.mean(-1, keepdim=True)
+    var = xg.var(-1, unbiased=False, keepdim=True)
+    xhat = ((xg - mean) / torch.sqrt(var + eps)).view_as(x)
+    if gamma.dim() == 1:
+        gamma, beta = gamma.expand(N, Cc), beta.expand(N, Cc)
+    y = xhat * gamma[:, :, None, None] + beta[:, :, None, None]
+    return F.silu(y) if silu else y
+
+
+def ref_attention(q, k, v, heads, scale):
+    """o[n, h*dv + c, i] = sum_j v[n, h*dv + c, j] softmax_j(scale * q[n, h*d:, i] . k[n, h*d:, j]) in fp64."""
+    N, Cq, H, W = q.shape
+    T = H * W
+    qd, kd, vd = (t.reshape(N * heads, -1, T) for t in (q, k, v))
+    pr = (scale * torch.bmm(qd.transpose(1, 2), kd)).softmax(-1)
+    return torch.bmm(vd, pr.transpose(1, 2)).reshape(N, -1, H, W)

@@ -2371,3 +2371,67 @@ def test_committed_pmc_traffic_was_measured_on_these_kernel_sources():
         assert pm.get('_config', 'cifar256') == cfg, cand[-1]
         dom = [k for k, v in pm.items() if isinstance(v, dict) and 'FETCH_SIZE' in v and 'WRITE_SIZE' in v]
         assert dom, cand[-1]
+
+
+@pytest.mark.parametrize('case', ['3x3', 'ups', 's2_asym', 's2_sym', 'same_2x2', '1x1_4x4'])
+def test_launch_parity_subset_references_equal_full_fp64(case):
+    """The structured-subset fp64 references of tests/test_launch_parity_gpu.py (tests/helpers.py) are the matching slices of the
+    full fp64 computation: forward and input gradient on the edge images, the weight gradient on the edge row x column tiles
+    (reduced over every image), GroupNorm forward / backward incl. the per-image affine gradients, attention; and the edge
+    index sets hold what they claim (first / last tile incl. a tail, both sides of the first 128-pixel tile boundary)."""
+    import torch.nn.functional as F
+    from helpers import edge_images, edge_tiles, ref_attention, ref_conv_dgrad, ref_conv_fwd, ref_conv_wgrad, ref_groupnorm
+    ops = pkg('ops')
+    assert edge_tiles(179, 64) == list(range(64)) + list(range(128, 179)) and edge_tiles(40, 32) == list(range(40))
+    assert edge_images(256, 16) == [0, 7, 8, 255] and edge_images(256, 64) == [0, 1, 2, 255] and edge_images(256, 1024) == [0, 255]
+    assert edge_images(1, 16) == [0]
+    spec, N, Cin, Cout, H = {'3x3': (ops.ConvSpec(3, 1, 1, 0), 10, 40, 70, 8), 'ups': (ops.ConvSpec(3, 1, 1, 1), 5, 24, 33, 4),
+                             's2_asym': (ops.ConvSpec(3, 2, 0, 0), 6, 36, 20, 8), 's2_sym': (ops.ConvSpec(3, 2, 1, 0), 6, 36, 20, 8),
+                             'same_2x2': (ops.ConvSpec.same(2, 2, 1, 0), 7, 20, 90, 6),
+                             '1x1_4x4': (ops.ConvSpec(1, 1, 0, 0), 40, 100, 67, 4)}[case]
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(N, Cin, H, H, generator=g, dtype=torch.float64)
+    w = torch.randn(Cout, Cin, spec.kh, spec.kw, generator=g, dtype=torch.float64).requires_grad_(True)
+    # full fp64 reference by autograd through the plain F.conv2d definition of each geometry
+    xv = x.repeat_interleave(2, 2).repeat_interleave(2, 3) if spec.ups else x
+    xv = xv.clone().requires_grad_(True)
+    if spec.keep:
+        xp = F.pad(xv, (spec.pad_w, spec.kw - 1 - spec.pad_w, spec.pad_h, spec.kh - 1 - spec.pad_h))
+        y = F.conv2d(xp, w)
+    elif spec.stride == 2 and spec.pad == 0:
+        y = F.conv2d(F.pad(xv, (0, 1, 0, 1)), w, stride=2)
+    else:
+        y = F.conv2d(xv, w, stride=spec.stride, padding=spec.pad)
+    assert y.shape[2:] == spec.out_hw(H, H)
+    dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+    y.backward(dy)
+    imgs = edge_images(N, y.shape[2] * y.shape[3])
+    assert torch.allclose(ref_conv_fwd(x[imgs], w.detach(), spec), y.detach()[imgs], rtol=1e-12, atol=1e-12)
+    dimgs = edge_images(N, xv.shape[2] * xv.shape[3])
+    assert torch.allclose(ref_conv_dgrad(dy[dimgs], w.detach(), spec, tuple(xv.shape[2:])), xv.grad[dimgs], rtol=1e-12, atol=1e-12)
+    rows, cols = edge_tiles(Cout, 64), edge_tiles(Cin, 32)
+    got = ref_conv_wgrad(dy[:, rows], x[:, cols], spec, spec.kh, spec.kw, max_elems=5000)      # several image chunks
+    assert torch.allclose(got, w.grad[rows][:, cols], rtol=1e-10, atol=1e-10)
+    # GroupNorm (+ SiLU) with per-image affine gradients, attention over channel-major tokens
+    G, C = 8, 48
+    xg = torch.randn(N, C, H, H, generator=g, dtype=torch.float64).requires_grad_(True)
+    gm, bt = (1 + 0.2 * torch.randn(C, generator=g, dtype=torch.float64)).requires_grad_(True), torch.randn(C, generator=g, dtype=torch.float64).requires_grad_(True)
+    z = F.silu(F.group_norm(xg, G, gm, bt, 1e-6))
+    dz = torch.randn(z.shape, generator=g, dtype=torch.float64)
+    z.backward(dz)
+    gi = edge_images(N, H * H)
+    xr = xg.detach()[gi].clone().requires_grad_(True)
+    gmi = gm.detach()[None].repeat(len(gi), 1).requires_grad_(True)
+    bti = bt.detach()[None].repeat(len(gi), 1).requires_grad_(True)
+    zr = ref_groupnorm(xr, gmi, bti, G, 1e-6, True)
+    zr.backward(dz[gi])
+    assert torch.allclose(zr, z.detach()[gi], atol=1e-12) and torch.allclose(xr.grad, xg.grad[gi], atol=1e-10)
+    if len(gi) == N:           # the per-image affine gradients sum to the full ones when every image is in the subset
+        assert torch.allclose(gmi.grad.sum(0), gm.grad, atol=1e-10) and torch.allclose(bti.grad.sum(0), bt.grad, atol=1e-10)
+    yg = F.group_norm(xg.detach(), G, gm.detach(), bt.detach(), 1e-6)
+    dyg = dz * torch.sigmoid(yg) * (1 + yg * (1 - torch.sigmoid(yg)))               # dL/d(affine output), per image
+    assert torch.allclose(bti.grad, dyg[gi].sum((2, 3)), atol=1e-10)
+    q, k, v = (torch.randn(N, 2 * 12, H, H, generator=g, dtype=torch.float64) for _ in range(3))
+    full = F.scaled_dot_product_attention(q.view(N, 2, 12, -1).transpose(2, 3), k.view(N, 2, 12, -1).transpose(2, 3),
+                                          v.view(N, 2, 12, -1).transpose(2, 3), scale=0.3).transpose(2, 3).reshape(q.shape)
+    assert torch.allclose(ref_attention(q[gi], k[gi], v[gi], 2, 0.3), full[gi], atol=1e-12)

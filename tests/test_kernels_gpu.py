@@ -1329,14 +1329,27 @@ def test_conv_wgrad_winograd_f3x3_2x2_matches_fp64(ops, report, monkeypatch, N, 
     gw2 = g0.clone()
     ops.conv_wgrad(dy, xa, xb, gw2, spec, alpha=0.5, accumulate=True)
     assert used == [True, True], used
-    # other split counts (the default aims at ~1024 workgroups): one slice, and as many as there are K tiles
-    e_split = {}
+    # other split counts (the default aims at WGRAD_WINO2D_BLOCKS = 512 workgroups): one slice -- the in-kernel accumulate path, no
+    # reduction launch -- and as many as _conv_wgrad_wino2d allows (one per four 64-pixel K tiles); the split count a run took is
+    # read off the size of the partials workspace it asked for (none: one slice)
+    assert ops.WGRAD_WINO2D_BLOCKS == 512
+    n = Cout * (C1 + C2) * 9
+    nt = N * Hh * Ww // 64
+    e_split, n_split = {}, {}
+    real_ws = ops._workspace
     for blocks in (1, 1 << 20):
-        monkeypatch.setattr(ops, 'WGRAD_BLOCKS', blocks)
+        monkeypatch.setattr(ops, 'WGRAD_WINO2D_BLOCKS', blocks)
+        sizes = []
+        monkeypatch.setattr(ops, '_workspace', lambda k, dev: (sizes.append(k), real_ws(k, dev))[1])
         gs = g0.clone()
         ops.conv_wgrad(dy, xa, xb, gs, spec, alpha=0.5, accumulate=True)
-        e_split[blocks] = relerr(gs - g0, ref)
-    monkeypatch.setattr(ops, 'WGRAD_BLOCKS', 1024)
+        monkeypatch.setattr(ops, '_workspace', real_ws)
+        assert all(k % n == 0 for k in sizes), sizes
+        e_split[blocks], n_split[blocks] = relerr(gs - g0, ref), max([k // n for k in sizes] + [1])
+    monkeypatch.setattr(ops, 'WGRAD_WINO2D_BLOCKS', 512)
+    assert used == [True] * 4, used
+    s_max = max(1, nt // 4)
+    assert n_split[1] == 1 and n_split[1 << 20] == -(-nt // -(-nt // s_max)), (n_split, nt)
     monkeypatch.setattr(ops, 'WGRAD_WINO2D', False)
     g1 = g0.clone()
     ops.conv_wgrad(dy, xa, xb, g1, spec, alpha=0.5, accumulate=True)
@@ -1345,6 +1358,6 @@ def test_conv_wgrad_winograd_f3x3_2x2_matches_fp64(ops, report, monkeypatch, N, 
     ops.conv_wgrad(dy, xa, xb, gd, spec, alpha=0.5, accumulate=True)
     e_w, e_1, e_d = relerr(gw - g0, ref), relerr(g1 - g0, ref), relerr(gd - g0, ref)
     report['wgrad/winograd_f3x3_2x2/%d_%d_%d_%s' % (N, C1 + C2, Cout, H)] = dict(wino2d=e_w, wino1d=e_1, direct=e_d, splits=e_split,
-                                                                             run_to_run_equal=bool(torch.equal(gw, gw2)))
+                                                                             split_counts=n_split, run_to_run_equal=bool(torch.equal(gw, gw2)))
     assert torch.equal(gw, gw2)
     assert e_w < 5e-6 and max(e_split.values()) < 5e-6, (e_w, e_split, e_1, e_d)
