@@ -126,6 +126,8 @@ SIGNATURES = {
     'dp_timestep_embedding': [_vp, _i, _i, _i, _f, _f, _vp, _vp],
     'dp_add_noise': [_vp, _vp, _vp, _vp, _i, _ll, _vp, _vp],
     'dp_mse_fwd_bwd': [_vp, _vp, _ll, _f, _vp, _vp, _i, _vp, _vp],
+    'dp_kd_fwd_bwd': [_vp, _vp, _vp, _ll, _f, _f, _f, _vp, _vp, _i, _vp],
+    'dp_kd_terms': [_vp, _i, _f, _f, _f, _vp, _vp],
     'dp_early_exit_update': [_vp, _f, _vp, _vp, _i, _vp],
     'dp_zero_if_stopped': [_vp, _ll, _vp, _vp],
     'dp_early_exit_update_ratio': [_vp, _f, _vp, _vp, _i, _vp],

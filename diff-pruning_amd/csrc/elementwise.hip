@@ -223,6 +223,85 @@ extern "C" int dp_mse_fwd_bwd(const float* out, const float* noise, long long n,
 }
 
 // ---------------------------------------------------------------------------------------------
+// distillation loss (functions/losses.py:17-31): S = student output, T = frozen teacher output, e = noise
+//   dout = gscale * (w_kd (S - T) + w_eps (S - e));  partial[blk] = sum (S-T)^2,  partial[nblocks + blk] = sum (S-e)^2
+// Same fixed grid, contiguous per-block slice and per-thread summation order as mse_kernel: the eps partial of (w_kd, w_eps) =
+// (0, 1) is mse_kernel's partial bit for bit.  KD_UNROLL strided elements per thread per round: their 3 x KD_UNROLL loads are
+// issued before the first use (indices clamped into the slice, so every load is unconditional); the out-of-slice lanes of the
+// last round add an exact +0 to both sums and store nothing.
+// ---------------------------------------------------------------------------------------------
+#define KD_UNROLL 4
+__global__ __launch_bounds__(256) void kd_kernel(const float* __restrict__ S, const float* __restrict__ T,
+                                                 const float* __restrict__ E, long long n, float w_kd, float w_eps, float gscale,
+                                                 float* __restrict__ dout, float* __restrict__ partial) {
+    __shared__ float red[4];
+    const long long per = (n + gridDim.x - 1) / gridDim.x;
+    const long long lo = (long long)blockIdx.x * per;
+    long long hi = lo + per;
+    if (hi > n) hi = n;
+    float sk = 0.f, se = 0.f;
+    for (long long base = lo + threadIdx.x; base < hi; base += 256 * KD_UNROLL) {
+        float s[KD_UNROLL], t[KD_UNROLL], e[KD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < KD_UNROLL; ++u) {
+            const long long i = base + (long long)u * 256;
+            const long long j = i < hi ? i : hi - 1;          // hi > lo here: the slice is not empty
+            s[u] = S[j];
+            t[u] = T[j];
+            e[u] = E[j];
+        }
+#pragma unroll
+        for (int u = 0; u < KD_UNROLL; ++u) {
+            const long long i = base + (long long)u * 256;
+            const bool ok = i < hi;
+            const float dk = ok ? s[u] - t[u] : 0.f;
+            const float de = ok ? s[u] - e[u] : 0.f;
+            sk = fmaf(dk, dk, sk);                              // mse_kernel's `s += d * d` compiles to this fma: written
+            se = fmaf(de, de, se);                              // out so that the vectoriser cannot split it here
+            if (ok) dout[i] = gscale * (w_kd * dk + w_eps * de);
+        }
+    }
+    sk = dp_block_sum_256(sk, red);
+    se = dp_block_sum_256(se, red);
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = sk;
+        partial[gridDim.x + blockIdx.x] = se;
+    }
+}
+extern "C" int dp_kd_fwd_bwd(const float* out, const float* teacher, const float* noise, long long n, float w_kd, float w_eps,
+                             float gscale, float* dout, float* partial, int nblocks, void* stream) {
+    if (n <= 0 || nblocks <= 0 || !dout || !partial) return (int)hipErrorInvalidValue;
+    DP_LAUNCH(kd_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, out, teacher, noise, n, w_kd, w_eps, gscale, dout,
+              partial);
+    return DP_LAUNCH_CHECK();
+}
+
+// terms = [w_kd * kd + w_eps * eps, kd, eps] with kd / eps = scale * (sum of their nblocks partials), each summed in
+// sum_partials_kernel's order (so eps == dp_sum_partials of the same partials, and loss == eps for (0, 1))
+__global__ __launch_bounds__(256) void kd_terms_kernel(const float* __restrict__ partial, int n, float w_kd, float w_eps,
+                                                       float scale, float* __restrict__ terms) {
+    __shared__ float red[4];
+    float a = 0.f, b = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        a += partial[i];
+        b += partial[n + i];
+    }
+    a = dp_block_sum_256(a, red);
+    b = dp_block_sum_256(b, red);
+    if (threadIdx.x == 0) {
+        const float kd = a * scale, eps = b * scale;
+        terms[0] = w_kd * kd + w_eps * eps;
+        terms[1] = kd;
+        terms[2] = eps;
+    }
+}
+extern "C" int dp_kd_terms(const float* partial, int nblocks, float w_kd, float w_eps, float scale, float* terms, void* stream) {
+    if (nblocks <= 0) return (int)hipErrorInvalidValue;
+    DP_LAUNCH(kd_terms_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nblocks, w_kd, w_eps, scale, terms);
+    return DP_LAUNCH_CHECK();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Diff-Pruning early exit on the device (ddpm_prune.py:104-106 / ddpm_exp/prune.py:249-256), fp32 like the reference's
 // 0-d tensors:  if (loss > loss_max) loss_max = loss;  if (loss < loss_max * thr) stop.
 // state = [loss_max, stopped (0/1), executed steps]; the loss of executed step k is kept in losses[k].

@@ -1427,6 +1427,25 @@ def mse_fwd_bwd(out, noise, gscale, loss_scale, want_grad=True, stop_state=None)
     return loss, dout
 
 
+def kd_fwd_bwd(out, teacher_out, noise, w_kd, w_eps, gscale, loss_scale, nblocks=MSE_BLOCKS):
+    """Distillation loss (functions/losses.py:17-31) of the student output `out` against the frozen teacher's output and the noise.
+    Returns (terms[3] device tensor = [w_kd * kd + w_eps * eps, kd, eps] with kd = loss_scale * sum (T - S)^2,
+    eps = loss_scale * sum (e - S)^2, dout = gscale * (w_kd (S - T) + w_eps (S - e))).  Two launches, no host read-back;
+    (w_kd, w_eps) = (0, 1) gives mse_fwd_bwd's loss and dout bit for bit."""
+    n = out.numel()
+    for x in (out, teacher_out, noise):
+        assert x.is_contiguous() and x.dtype == _f32 and x.is_cuda and x.numel() == n and x.device == out.device, \
+            'kd_fwd_bwd takes fp32 device tensors of equal size'
+    dout = empty_act(tuple(out.shape), out.device)
+    partial = torch.empty(2 * nblocks, dtype=_f32, device=out.device)
+    terms = torch.empty(3, dtype=_f32, device=out.device)
+    L.check(_lib().dp_kd_fwd_bwd(_p(out), _p(teacher_out), _p(noise), n, float(w_kd), float(w_eps), float(gscale), _p(dout),
+                                 _p(partial), int(nblocks), _stream()), 'dp_kd_fwd_bwd')
+    L.check(_lib().dp_kd_terms(_p(partial), int(nblocks), float(w_kd), float(w_eps), float(loss_scale), _p(terms), _stream()),
+            'dp_kd_terms')
+    return terms, dout
+
+
 def early_exit_update(loss, thr, state, losses):
     """state = [loss_max, stopped, steps] (device, fp32), losses[k] = loss of executed step k; see include/dp_hip.h."""
     L.check(_lib().dp_early_exit_update(_p(loss), float(thr), _p(state), _p(losses), losses.numel(), _stream()),

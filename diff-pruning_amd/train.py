@@ -10,8 +10,13 @@ Philox functions of (seed, layer, optimizer step, global element index): fused i
 in the backward pass, independent of how the batch is sharded over ranks (csrc/dp_common.h).
 LR schedule: diffusers/optimization.py:282 `get_scheduler` (LambdaLR multipliers), stepped once per optimizer step
 (ddpm_train.py:340-346,464).
+Distillation (ddpm_exp/finetune.py --kd, runners/diffusion.py:197-217,301-302, functions/losses.py:17-31): with a frozen
+`teacher` the loss is w_kd * mean_b sum_chw (T - S)^2 + w_eps * mean_b sum_chw (e - S)^2 (0.7 / 0.3), T the teacher's no-grad
+forward of the same noisy input -- on the side stream, concurrently with the student's forward, when DP_KD_OVERLAP says so.
 """
 import math
+import numbers
+import os
 
 import torch
 
@@ -134,9 +139,67 @@ def _require_hip_device(dev):
         raise RuntimeError('finetune runs on the MI355X HIP kernels only')
 
 
+def _check_kd_weights(kd_weights):
+    try:
+        w = tuple(kd_weights)
+    except TypeError:
+        w = None
+    if w is None or len(w) != 2 or not all(isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(x) for x in w):
+        raise ValueError('kd_weights must be two finite numbers (w_kd, w_eps), got %r' % (kd_weights,))
+    return float(w[0]), float(w[1])
+
+
+def _check_teacher(teacher, student, dev):
+    from .unet import UNet2DModel
+    if not isinstance(teacher, UNet2DModel):
+        raise TypeError('teacher must be a UNet2DModel (train.load_teacher converts checkpoints), got %s' % type(teacher).__name__)
+    if teacher is student:
+        raise ValueError('the teacher must not be the student model itself')
+    tdev = next(teacher.parameters()).device
+    if tdev != dev:
+        raise ValueError('the teacher is on %s, the student on %s' % (tdev, dev))
+    for k in ('in_channels', 'out_channels', 'sample_size'):
+        if teacher.config[k] != student.config[k]:
+            raise ValueError('teacher %s = %r does not match the student\'s %r' % (k, teacher.config[k], student.config[k]))
+
+
+def load_teacher(src, device, ch=None, ch_mult=None, num_res_blocks=None, attn_resolutions=None, image_size=None,
+                 in_channels=3, out_ch=3):
+    """The frozen teacher of a distillation finetune as a UNet2DModel on `device` (eval mode, parameters frozen).
+    src: a UNet2DModel; a Diffusers model / pipeline directory (checkpoint.load_unet); or an original-DDPM checkpoint -- a
+    `Model` state dict, the `[state_dict, ...]` list the reference unpacks with `states[0]` (runners/diffusion.py:207-211), or
+    a file holding either -- together with that model's ch / ch_mult / num_res_blocks / attn_resolutions / image_size
+    (ddpm_exp/configs/*.yml), converted with checkpoint.convert_ddpm_original."""
+    from . import checkpoint
+    from .unet import UNet2DModel
+    if isinstance(src, UNet2DModel):
+        model = src
+    elif isinstance(src, (str, os.PathLike)) and os.path.isdir(src):
+        model = checkpoint.load_unet(os.fspath(src))
+    else:
+        states = torch.load(os.fspath(src), map_location='cpu', weights_only=True) if isinstance(src, (str, os.PathLike)) else src
+        sd = states[0] if isinstance(states, (list, tuple)) else states
+        if not isinstance(sd, dict):
+            raise TypeError('load_teacher: expected a UNet2DModel, a model directory, an original-DDPM state dict or a '
+                            '[state_dict, ...] list, got %s' % type(sd).__name__)
+        arch = (ch, ch_mult, num_res_blocks, attn_resolutions, image_size)
+        if any(a is None for a in arch):
+            raise ValueError('load_teacher: an original-DDPM checkpoint needs ch, ch_mult, num_res_blocks, attn_resolutions and '
+                             'image_size (ddpm_exp/configs/*.yml)')
+        cfg = checkpoint.unet2d_config_from_ddpm_original(ch, list(ch_mult), num_res_blocks, list(attn_resolutions), image_size,
+                                                          in_channels, out_ch)
+        model = UNet2DModel(**cfg)
+        model.load_state_dict(checkpoint.convert_ddpm_original(sd), strict=True)
+    model = model.to(device).eval()
+    for p in model.parameters():
+        p.requires_grad_(False)
+    return model
+
+
 class FinetuneEngine:
     def __init__(self, model, scheduler, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, ema_decay=0.9999, max_grad_norm=1.0,
-                 use_ema=True, group=None, dropout=None, lr_scheduler=None, dropout_seed=0, replay=None):
+                 use_ema=True, group=None, dropout=None, lr_scheduler=None, dropout_seed=0, replay=None, teacher=None,
+                 kd_weights=(0.7, 0.3)):
         """dropout: None keeps whatever `set_dropout(model, p)` has set on the nn.Dropout holders; a float sets it.
         lr_scheduler: a `LambdaLR` from `get_scheduler` (its base_lr is the learning rate) or None (constant `lr`).
         replay: True / False / None (automatic: single-process steps on a cuda device, DP_FINETUNE_REPLAY=0 disables) -- the step is
@@ -144,7 +207,14 @@ class FinetuneEngine:
         (ops.CapturedCall): ~750 launches without Python / ctypes per launch.  What changes from step to step lives on the device:
         inputs and timesteps in static buffers, {lr, Adam bias corrections, optimizer step (= the dropout masks' step)} in a
         4-word buffer written by ONE by-value launch per step (ops.set_step_scalars); the weight re-packing is part of the
-        captured step.  Same kernels, arguments and order as the eager step -> the same bits."""
+        captured step.  Same kernels, arguments and order as the eager step -> the same bits.
+        teacher: None (the eps loss), or a frozen UNet2DModel on the model's device whose no-grad forward of the same noisy input
+        enters the distillation loss with weights kd_weights = (w_kd, w_eps) (functions/losses.py:17-31).  It runs in eval mode
+        without dropout; its packed operands are built once and kept (it is never written); EMA and the optimizer see the student
+        only.  `last_loss_terms` holds the [kd, eps] device tensor of the last step."""
+        if teacher is not None:
+            kd_weights = _check_kd_weights(kd_weights)
+            _check_teacher(teacher, model, next(model.parameters()).device)
         self.replay = replay
         self._caps = None            # {capture key: captured step} (_step_replayed)
         self._seen = {}              # {batch shape: eager steps run at it}
@@ -188,6 +258,15 @@ class FinetuneEngine:
         self.step_count = 0
         self.acp = scheduler._acp_on(dev)
         self.last_grad_norm = None
+        self.teacher, self.kd_weights, self.last_loss_terms = None, None, None
+        if teacher is not None:
+            teacher.eval()
+            for p in teacher.parameters():
+                p.requires_grad_(False)
+            self._teacher_pin = teacher.pin_weights()     # frozen for the engine's lifetime: its operands are packed once
+            self._teacher_pin.__enter__()
+            self._teacher_eng = self._teacher_pin.eng
+            self.teacher, self.kd_weights = teacher, kd_weights
 
     def ema_state(self):
         """EMA parameters as a {name: tensor} dict (views of the flat EMA buffer)."""
@@ -221,12 +300,41 @@ class FinetuneEngine:
         self._weights_changed()
 
     REPLAY_OVERLAP = None        # weight-gradient side stream inside the captured step: None = the engine's own rule (by step size)
+    # teacher forward on the side stream, beside the student's forward (DP_KD_OVERLAP=0 / 1 overrides).  [measured, C4 shapes,
+    # tools/bench_kd.py, replayed, one box] 31.13 ms per KD step serial, 29.40 overlapped: 5.6 % on each of three rounds
+    KD_OVERLAP = True
     MAX_CAPTURES = 2             # captured steps kept alive at once (full batch + the partial last batch of an epoch)
 
     @property
     def _cap(self):
         """The most recently built captured step, or None."""
         return next(reversed(self._caps.values())) if self._caps else None
+
+    def _kd_overlap(self, dev):
+        ov = os.environ.get('DP_KD_OVERLAP')
+        return dev.type == 'cuda' and (self.KD_OVERLAP if ov is None else ov != '0')
+
+    def _teacher_forward(self, noisy, t, overlap, slot):
+        """The frozen teacher's no-grad forward of the student's input (eval mode: no dropout, packed operands pinned).
+        overlap: fork onto the engine's process-lifetime side stream (idle during the forward; the student's forward goes on on
+        the current stream) -- the caller joins with _teacher_join before anything reads the result.  `noisy` and `t` are
+        alive until that join (the caller holds them); what the side stream allocates goes back to its own pool, whose next
+        user (the next fork) is ordered after the join."""
+        teng = self._teacher_eng
+        teng.set_dropout(None)
+        if not overlap:
+            return teng.forward(noisy, t, save=False), None
+        from .engine import shared_stream, _low_priority_stream
+        side = shared_stream(noisy.device, 'wgrad', slot, _low_priority_stream)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            out = teng.forward(noisy, t, save=False)
+        return out, side
+
+    @staticmethod
+    def _teacher_join(side):
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
 
     def _replay_wanted(self, use_dist, dev):
         import os
@@ -244,6 +352,9 @@ class FinetuneEngine:
         # everything the captured launches carry as immediate arguments: a change of any of them builds a new capture
         key = (tuple(clean.shape), int(image_offset), int(gb), tuple(sorted(table.items())), int(self.dropout_seed),
                self.max_grad_norm, self.eps, self.ema_decay, tuple(self.betas))
+        kd_overlap = self._kd_overlap(dev) if self.teacher is not None else False
+        if self.teacher is not None:
+            key = key + (('kd', id(self.teacher), self.kd_weights, kd_overlap),)
         if self._caps is None:
             self._caps = {}
         cap = self._caps.get(key)
@@ -275,9 +386,16 @@ class FinetuneEngine:
                     eng.overlap_wgrad = overlap
                 eng.prepare_packs()                       # the optimizer update of the previous replay invalidated every operand
                 noisy = ops.add_noise(st['clean'], st['noise'], self.acp, st['t'])
+                if self.teacher is not None:
+                    t_out, side = self._teacher_forward(noisy, st['t'], kd_overlap, eng.stream_slot)
                 self.flat_g.zero_()
                 out = eng.forward(noisy, st['t'], save=True)
-                loss, dout = ops.mse_fwd_bwd(out, st['noise'], 2.0 / gb, 1.0 / gb)
+                if self.teacher is None:
+                    loss, dout = ops.mse_fwd_bwd(out, st['noise'], 2.0 / gb, 1.0 / gb)
+                else:
+                    self._teacher_join(side)
+                    loss, dout = ops.kd_fwd_bwd(out, t_out, st['noise'], self.kd_weights[0], self.kd_weights[1], 2.0 / gb, 1.0 / gb)
+                    del t_out
                 eng.backward(dout)
                 nc = ops.clip_coef(ops.sumsq_partials(self.flat_g), self.max_grad_norm)
                 ops.adam_ema_dev(self.flat_p, self.flat_g, self.m, self.v, self.ema, nc[1:2], hyper, self.betas[0], self.betas[1],
@@ -285,11 +403,16 @@ class FinetuneEngine:
                 eng.packs.clear()                         # host bookkeeping: nothing packed here outlives the step
                 return loss, nc
             saved_overlap = eng.overlap_wgrad
+            packs_before = self._teacher_packs() if self.teacher is not None else None
             try:
                 st['call'] = ops.CapturedCall(body, side_stream=eng.replay_side_stream(dev))
             finally:
                 eng.overlap_wgrad = saved_overlap
                 eng.set_dropout(None)
+            if packs_before is not None and not self._same_packs(packs_before, self._teacher_packs()):
+                # the eager step before every capture packed all of them: a pack recorded into the capture would be re-run by
+                # every replay into a buffer the capture's pool owns
+                raise RuntimeError('the teacher\'s packed operands changed inside the captured step')
             self._caps[key] = cap = st
         if clean.data_ptr() != cap['clean'].data_ptr():
             cap['clean'].copy_(clean)
@@ -307,9 +430,21 @@ class FinetuneEngine:
         eng = getattr(model, '_engine', None)
         if eng is not None:
             eng.packs.clear()
-        loss = loss.clone()                                # the captured tensor is overwritten by the next step
+        if self.teacher is not None:
+            terms = loss.clone()                           # [loss, kd, eps]
+            loss, self.last_loss_terms = terms[0:1], terms[1:3]
+        else:
+            loss = loss.clone()                            # the captured tensor is overwritten by the next step
         self._throttle.mark()
         return loss
+
+    def _teacher_packs(self):
+        """A snapshot of the teacher's operand cache (pinned: filled by its first forward, then never rebuilt)."""
+        return dict(self._teacher_eng.packs._c)
+
+    @staticmethod
+    def _same_packs(a, b):
+        return a.keys() == b.keys() and all(a[k] is b[k] for k in a)
 
     def step(self, clean, noise, timesteps, global_batch=None, image_offset=None):
         """Returns the (local share of the) loss as a [1] device tensor; no host synchronisation.
@@ -343,9 +478,17 @@ class FinetuneEngine:
         eng.temb_batch = eng.temb_batch and not use_dist
         t = timesteps.to(device=dev, dtype=torch.long).contiguous()
         noisy = ops.add_noise(clean, noise, self.acp, t)
+        if self.teacher is not None:
+            t_out, side = self._teacher_forward(noisy, t, self._kd_overlap(dev), eng.stream_slot)
         self.flat_g.zero_()                               # optimizer.zero_grad()
         out = eng.forward(noisy, t, save=True)
-        loss, dout = ops.mse_fwd_bwd(out, noise, 2.0 / gb, 1.0 / gb)
+        if self.teacher is None:
+            loss, dout = ops.mse_fwd_bwd(out, noise, 2.0 / gb, 1.0 / gb)
+        else:
+            self._teacher_join(side)
+            terms, dout = ops.kd_fwd_bwd(out, t_out, noise, self.kd_weights[0], self.kd_weights[1], 2.0 / gb, 1.0 / gb)
+            loss, self.last_loss_terms = terms[0:1], terms[1:3]
+            del t_out
         pending = []
         if use_dist:
             # bucketed all-reduce overlapped with the backward pass: each bucket's collective (RCCL over xGMI) is enqueued as

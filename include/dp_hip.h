@@ -280,6 +280,13 @@ int dp_add_noise(const float* x0, const float* noise, const float* acp, const in
  * F.mse_loss (ddpm_prune.py:101): gscale = 2/numel;  sum-CHW/mean-B loss (ddpm_train.py:459): gscale = 2/B. */
 int dp_mse_fwd_bwd(const float* out, const float* noise, long long n, float gscale, float* dout, float* partial, int nblocks,
                    const float* stop_state, void* stream);
+/* Distillation loss (functions/losses.py:17-31) with S = out (student), T = teacher (frozen teacher's output), e = noise:
+ * dout = gscale * (w_kd (S - T) + w_eps (S - e));  partial[block] = sum (S-T)^2, partial[nblocks + block] = sum (S-e)^2 over the
+ * block's slice (dp_mse_fwd_bwd's fixed grid and summation order: (w_kd, w_eps) = (0, 1) reproduces it bit for bit).
+ * dp_kd_terms: terms[3] = [w_kd kd + w_eps eps, kd, eps], kd / eps = scale * sum of their partials (dp_sum_partials' order). */
+int dp_kd_fwd_bwd(const float* out, const float* teacher, const float* noise, long long n, float w_kd, float w_eps, float gscale,
+                  float* dout, float* partial, int nblocks, void* stream);
+int dp_kd_terms(const float* partial, int nblocks, float w_kd, float w_eps, float scale, float* terms, void* stream);
 /* Diff-Pruning early exit kept on the device (ddpm_prune.py:104-106: `if loss > loss_max: loss_max = loss; if loss <
  * loss_max * thr: break`, fp32 as the reference's 0-d tensors).  state = [loss_max, stopped, executed steps] (zero-initialised),
  * losses[k] = loss of executed step k.  Once stopped, dp_mse_fwd_bwd(stop_state = state) produces dOut = 0, so timesteps the
