@@ -135,6 +135,7 @@ def unet_forward(P, cfg, sample, timesteps, drop=None):
         timesteps = timesteps[None].to(sample.device)
     timesteps = timesteps * torch.ones(sample.shape[0], dtype=timesteps.dtype, device=timesteps.device)
     t_emb = timestep_embedding(timesteps, boc[0], cfg['flip_sin_to_cos'], cfg['freq_shift'])
+    t_emb = t_emb.to(P['time_embedding.linear_1.weight'].dtype)      # unet_2d.py:258: the fp32 embedding cast to the model's dtype
     emb = _lin(P, 'time_embedding.linear_2', F.silu(_lin(P, 'time_embedding.linear_1', t_emb)))
 
     x = _conv(P, 'conv_in', sample)

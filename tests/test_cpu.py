@@ -2435,3 +2435,75 @@ def test_launch_parity_subset_references_equal_full_fp64(case):
     full = F.scaled_dot_product_attention(q.view(N, 2, 12, -1).transpose(2, 3), k.view(N, 2, 12, -1).transpose(2, 3),
                                           v.view(N, 2, 12, -1).transpose(2, 3), scale=0.3).transpose(2, 3).reshape(q.shape)
     assert torch.allclose(ref_attention(q[gi], k[gi], v[gi], 2, 0.3), full[gi], atol=1e-12)
+
+
+# ----------------------------------------------------------------------------------- full-size sampling (teacher-forced)
+def _c1_pruned_oracle_params(dtype):
+    """The seeded CIFAR parameters with the reference's C1 pruned index lists (cifar_c1.json) sliced out, group by group: the
+    parameters of the ratio-0.3 pruned model without running the sweep again."""
+    from oracle import pruning_ref as R
+    G = pkg('graph')
+    fx = load_json('cifar_c1.json')
+    P = {n: t.to(dtype) for n, t in oracle_params(gc.CIFAR_CFG, 0, requires_grad=False).items()}
+    gr = G.UNetGraph(gc.CIFAR_CFG)
+    for r in fx['prune']:
+        for m in G.coupled_members(gr, G.ChannelView({n: tuple(t.shape) for n, t in P.items()}), r['root'], r['pruned']):
+            R.slice_member(P, {}, m.name, 'gn' if m.kind == 'ln' else m.kind, m.idxs)
+    assert {n: list(t.shape) for n, t in P.items()} == fx['shapes_after']
+    assert sum(t.numel() for t in P.values()) == 19851157
+    return P
+
+
+def _fp64_matches_fixture(got64, fixture32, sums=None):
+    """`got64` (fp64) against an fp64 result the reference wrote rounded to fp32: within half an fp32 ulp of the stored value (+1e-9),
+    and, where the fixture kept them, the fp64 sum / abs-sum / sum of squares of the unrounded result to 1e-9 relative."""
+    ref = torch.from_numpy(fixture32).double()
+    half_ulp = torch.from_numpy(np.spacing(np.abs(fixture32)).astype(np.float64)) / 2
+    err = float(((got64 - ref).abs() - half_ulp).max())
+    assert err <= 1e-9, err
+    if sums is not None:
+        mine = [float(got64.sum()), float(got64.abs().sum()), float((got64 * got64).sum())]
+        for a, b in zip(mine, sums):
+            assert abs(a - b) <= 1e-9 * max(1.0, abs(b)), (mine, list(sums))
+
+
+@pytest.mark.parametrize('model', ['full', 'pruned'])
+def test_oracle_reproduces_full_size_sampling_fixtures(model):
+    """tests/golden/sampling_cifar*.npz (make_golden_sampling.py): the reference's fp64 eps and DDIMScheduler.step outputs on x_k of
+    its fp64 100-step trajectory of the full-size CIFAR UNet and of the C1 ratio-0.3 pruned one.  The oracle in fp64
+    (unet_ref.unet_forward, diffusion_ref.ddim_step) reproduces them at three stored steps (t = 999, 494 and 0, where the step uses
+    final_alpha_cumprod); on the full model also the eta 0.5, quad-schedule and DDPM (t = 999, 500, 1, 0) steps."""
+    from oracle import diffusion_ref as D, unet_ref as U
+    g = load_npz('sampling_cifar.npz' if model == 'full' else 'sampling_cifar_pruned.npz')
+    P = ({n: t.double() for n, t in oracle_params(gc.CIFAR_CFG, int(g['model_seed']), requires_grad=False).items()}
+         if model == 'full' else _c1_pruned_oracle_params(torch.float64))
+    assert sum(t.numel() for t in P.values()) == int(g['params'])
+    acp = D.alphas_cumprod()
+    steps = [int(k) for k in g['steps']]
+    n = int(g['n_steps'])
+    assert np.array_equal(D.ddim_timesteps(n).numpy()[steps], g['timesteps'])
+    with torch.no_grad():
+        for i in (steps.index(0), steps.index(50), steps.index(99)):
+            t = int(g['timesteps'][i])
+            x = torch.from_numpy(g['x'][i]).double()
+            eps = U.unet_forward(P, gc.CIFAR_CFG, x, torch.tensor([t]))
+            _fp64_matches_fixture(eps, g['eps'][i], g['eps_sums'][i])
+            _fp64_matches_fixture(D.ddim_step(acp, eps, t, x, n), g['out'][i], g['out_sums'][i])
+        if model == 'pruned':
+            return
+        e = load_npz('sampling_cifar_edges.npz')
+        for kind in ('eta', 'quad', 'ddpm'):
+            for j in range(int(e['n_' + kind])):
+                f = lambda k: e['%s:%d:%s' % (kind, j, k)]
+                t = int(f('t'))
+                x = torch.from_numpy(f('x')).double()
+                eps = U.unet_forward(P, gc.CIFAR_CFG, x, torch.tensor([t]))
+                _fp64_matches_fixture(eps, f('eps'))
+                if kind == 'eta':
+                    out = D.ddim_step(acp, eps, t, x, n, eta=float(e['eta']), variance_noise=torch.from_numpy(f('noise')).double())
+                elif kind == 'quad':
+                    assert int(e['quad_timesteps'][int(f('step'))]) == t == int(D.ddim_timesteps(n, skip_type='quad')[int(f('step'))])
+                    out = D.ddim_step(acp, eps, t, x, n)
+                else:
+                    out = D.ddpm_step(acp, eps, t, x, 1000, variance_noise=torch.from_numpy(f('noise')).double())
+                _fp64_matches_fixture(out, f('out'), f('out_sums'))
