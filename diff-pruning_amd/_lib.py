@@ -165,6 +165,9 @@ SIGNATURES = {
     'dp_ssim': [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     'dp_ssim_workspace': [_i, _i, _i, _i],
     'dp_mse_per_image': [_vp, _vp, _i, _ll, _vp, _vp],
+    'dp_vq_blocks': [_ll],
+    'dp_vq_quantize': [_vp, _ll, _i, _i, _ll, _vp, _i, _vp, _ll, _vp, _vp, _vp],
+    'dp_vq_loss': [_vp, _i, C.c_double, _vp, _vp],
     'dp_replay_build': [_vp, C.POINTER(C.c_void_p)],
     'dp_replay_launch': [_vp, _vp, _vp],
     'dp_replay_info': [_vp, C.POINTER(C.c_int)],

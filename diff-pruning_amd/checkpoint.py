@@ -255,6 +255,34 @@ def _write_json(path, obj):
         f.write('\n')
 
 
+_DEPRECATED_ATTN = (('query', 'to_q'), ('key', 'to_k'), ('value', 'to_v'), ('proj_attn', 'to_out.0'))
+
+
+def convert_deprecated_attention_keys(state_dict):
+    """modeling_utils.py:809-851: older checkpoints name the attention projections of `...attentions.<j>` query / key / value /
+    proj_attn; they are to_q / to_k / to_v / to_out.0 now.  A state dict without those names is returned as it is."""
+    import re
+    pat = re.compile(r'^(.*\.attentions\.\d+)\.(query|key|value|proj_attn)\.(weight|bias)$')
+    if not any(pat.match(k) for k in state_dict):
+        return state_dict
+    out = type(state_dict)() if isinstance(state_dict, dict) else {}
+    for k, v in state_dict.items():
+        m = pat.match(k)
+        out[('%s.%s.%s' % (m.group(1), dict(_DEPRECATED_ATTN)[m.group(2)], m.group(3))) if m else k] = v
+    return out
+
+
+def _load_weights(d):
+    for name in _UNET_WEIGHTS:
+        p = os.path.join(d, name)
+        if os.path.exists(p):
+            if name.endswith('.safetensors'):
+                from safetensors.torch import load_file
+                return load_file(p)
+            return torch.load(p, map_location='cpu', weights_only=True)
+    raise FileNotFoundError('no %s in %s' % (' / '.join(_UNET_WEIGHTS), d))
+
+
 def load_unet(directory, subfolder=None):
     """UNet2DModel.from_pretrained: `directory` (or its `subfolder`) holds config.json + the weight file."""
     from .unet import UNet2DModel
@@ -263,17 +291,8 @@ def load_unet(directory, subfolder=None):
         d = os.path.join(d, 'unet')
     cfg = {k: v for k, v in _read_json(os.path.join(d, 'config.json')).items() if not k.startswith('_')}
     model = UNet2DModel(**cfg)
-    for name in _UNET_WEIGHTS:
-        p = os.path.join(d, name)
-        if os.path.exists(p):
-            if name.endswith('.safetensors'):
-                from safetensors.torch import load_file
-                sd = load_file(p)
-            else:
-                sd = torch.load(p, map_location='cpu', weights_only=True)
-            model.load_state_dict(sd, strict=True)
-            return model.eval()
-    raise FileNotFoundError('no %s in %s' % (' / '.join(_UNET_WEIGHTS), d))
+    model.load_state_dict(convert_deprecated_attention_keys(_load_weights(d)), strict=True)
+    return model.eval()
 
 
 def save_unet(model, directory, safe_serialization=False):
@@ -307,6 +326,32 @@ def save_scheduler(scheduler, directory):
     _write_json(os.path.join(directory, 'scheduler_config.json'), cfg)
 
 
+def load_vq(directory, subfolder=None):
+    """VQModel.from_pretrained: `directory` (or its `subfolder`) holds config.json + the weight file; deprecated attention names
+    are converted as modeling_utils.py:809-851 does."""
+    from .vq import VQModel
+    d = os.path.join(directory, subfolder) if subfolder else directory
+    if not os.path.exists(os.path.join(d, 'config.json')) and os.path.exists(os.path.join(d, 'vqvae', 'config.json')):
+        d = os.path.join(d, 'vqvae')
+    cfg = {k: v for k, v in _read_json(os.path.join(d, 'config.json')).items() if not k.startswith('_')}
+    model = VQModel(**cfg)
+    model.load_state_dict(convert_deprecated_attention_keys(_load_weights(d)), strict=True)
+    return model.eval()
+
+
+def save_vq(model, directory, safe_serialization=False):
+    """VQModel.save_pretrained layout (config.json + diffusion_pytorch_model.bin, or .safetensors)."""
+    os.makedirs(directory, exist_ok=True)
+    cfg = dict(_config_dict(model), _class_name='VQModel', _diffusers_version=DIFFUSERS_VERSION)
+    _write_json(os.path.join(directory, 'config.json'), cfg)
+    sd = {k: v.detach().to('cpu').contiguous() for k, v in model.state_dict().items()}
+    if safe_serialization:
+        from safetensors.torch import save_file
+        save_file(sd, os.path.join(directory, _UNET_WEIGHTS[0]))
+    else:
+        torch.save(sd, os.path.join(directory, _UNET_WEIGHTS[1]))
+
+
 def load_pipeline(cls, directory):
     from . import diffusion
     index = _read_json(os.path.join(directory, 'model_index.json'))
@@ -314,12 +359,103 @@ def load_pipeline(cls, directory):
     sched_cls = getattr(diffusion, sched_name, None)
     if sched_cls is None:
         raise NotImplementedError('scheduler class %s' % sched_name)
-    return cls(unet=load_unet(directory, 'unet'), scheduler=load_scheduler(sched_cls, directory, 'scheduler'))
+    parts = dict(unet=load_unet(directory, 'unet'), scheduler=load_scheduler(sched_cls, directory, 'scheduler'))
+    if 'vqvae' in index:                                 # LDMPipeline (pipeline_latent_diffusion_uncond.py)
+        parts['vqvae'] = load_vq(directory, 'vqvae')
+    return cls(**parts)
 
 
 def save_pipeline(pipeline, directory, safe_serialization=False):
-    _write_json(os.path.join(directory, 'model_index.json'),
-                dict(_class_name=type(pipeline).__name__, _diffusers_version=DIFFUSERS_VERSION,
-                     scheduler=['diffusers', type(pipeline.scheduler).__name__], unet=['diffusers', 'UNet2DModel']))
+    index = dict(_class_name=type(pipeline).__name__, _diffusers_version=DIFFUSERS_VERSION,
+                 scheduler=['diffusers', type(pipeline.scheduler).__name__], unet=['diffusers', 'UNet2DModel'])
+    if getattr(pipeline, 'vqvae', None) is not None:
+        index['vqvae'] = ['diffusers', 'VQModel']
+        save_vq(pipeline.vqvae, os.path.join(directory, 'vqvae'), safe_serialization)
+    _write_json(os.path.join(directory, 'model_index.json'), index)
     save_unet(pipeline.unet, os.path.join(directory, 'unet'), safe_serialization)
     save_scheduler(pipeline.scheduler, os.path.join(directory, 'scheduler'))
+
+
+# --------------------------------------------------------------------------------------------------------
+# ldm_exp first stage (ldm/modules/diffusionmodules/model.py Encoder / Decoder, ldm/models/autoencoder.py VQModel) <-> VQModel
+# --------------------------------------------------------------------------------------------------------
+# `down.{i}` / `up.{i}` are indexed by resolution level in both Encoder and Decoder (0 = full resolution); Diffusers' decoder
+# `up_blocks.{j}` by execution order (0 = lowest resolution).  The attention projections are 1x1 Conv2d there, Linear here.
+_RES_L2D = (('norm1', 'norm1'), ('conv1', 'conv1'), ('norm2', 'norm2'), ('conv2', 'conv2'), ('nin_shortcut', 'conv_shortcut'))
+_ATT_L2D = (('norm', 'group_norm'), ('q', 'to_q'), ('k', 'to_k'), ('v', 'to_v'), ('proj_out', 'to_out.0'))
+
+
+def ldm_first_stage_key(key, up_levels):
+    """Diffusers VQModel key of one ldm_exp first-stage key (without the `first_stage_model.` prefix)."""
+    stem, _, leaf = key.rpartition('.')
+    p = stem.split('.')
+    top = {'quant_conv': 'quant_conv', 'post_quant_conv': 'post_quant_conv', 'quantize.embedding': 'quantize.embedding'}
+    new = None
+    if stem in top:
+        new = top[stem]
+    elif p[0] in ('encoder', 'decoder') and len(p) >= 2:
+        side = p[0]
+        rest = p[1:]
+        if rest[0] in ('conv_in', 'conv_out') and len(rest) == 1:
+            new = '%s.%s' % (side, rest[0])
+        elif rest == ['norm_out']:
+            new = side + '.conv_norm_out'
+        elif rest[0] == 'mid' and len(rest) >= 3:
+            if rest[1] in ('block_1', 'block_2'):
+                new = '%s.mid_block.resnets.%d.%s' % (side, int(rest[1][-1]) - 1, dict(_RES_L2D)[rest[2]])
+            elif rest[1] == 'attn_1':
+                new = '%s.mid_block.attentions.0.%s' % (side, dict(_ATT_L2D)[rest[2]])
+        elif rest[0] in ('down', 'up') and len(rest) >= 3:
+            i = int(rest[1])
+            blk = ('down_blocks.%d' % i) if rest[0] == 'down' else ('up_blocks.%d' % (up_levels - 1 - i))
+            if rest[2] == 'block' and len(rest) == 5:
+                new = '%s.%s.resnets.%s.%s' % (side, blk, rest[3], dict(_RES_L2D)[rest[4]])
+            elif rest[2] == 'downsample' and rest[3:] == ['conv']:
+                new = '%s.%s.downsamplers.0.conv' % (side, blk)
+            elif rest[2] == 'upsample' and rest[3:] == ['conv']:
+                new = '%s.%s.upsamplers.0.conv' % (side, blk)
+    if new is None:
+        raise KeyError('not an ldm_exp VQ first-stage parameter: %s' % key)
+    return new + '.' + leaf
+
+
+# training-only state of a standalone ldm_exp VQModel checkpoint (autoencoder.py:36-55): the loss module (discriminator, LPIPS),
+# the LitEma copy of the weights and the segmentation colouriser -- not part of the encode / quantize / decode network
+_LDM_TRAINING_ONLY = ('loss.', 'model_ema.', 'colorize')
+
+
+def convert_ldm_first_stage(state_dict):
+    """ldm_exp first-stage state dict -> state dict with this package's / Diffusers' VQModel keys.  Takes a LatentDiffusion
+    checkpoint (its `first_stage_model.*` entries; every other entry is skipped) or a standalone ldm_exp VQModel checkpoint (its
+    training-only `loss.*`, `model_ema.*` and `colorize` entries are skipped).  The 1x1-conv attention projections [C, C, 1, 1]
+    become Linear weights [C, C]."""
+    pre = 'first_stage_model.'
+    if any(k.startswith(pre) for k in state_dict):
+        state_dict = {k[len(pre):]: v for k, v in state_dict.items() if k.startswith(pre)}
+    state_dict = {k: v for k, v in state_dict.items() if not k.startswith(_LDM_TRAINING_ONLY)}
+    ups = [int(k.split('.')[2]) for k in state_dict if k.startswith('decoder.up.')]
+    levels = 1 + max(ups) if ups else 0
+    out = {}
+    for k, v in state_dict.items():
+        nk = ldm_first_stage_key(k, levels)
+        if '.attentions.' in nk and '.group_norm.' not in nk and v.dim() == 4:
+            v = v.reshape(v.shape[0], v.shape[1])
+        out[nk] = v
+    return out
+
+
+def vq_config_from_ldm(ddconfig, embed_dim, n_embed):
+    """VQModel kwargs equivalent to an ldm_exp first stage (first_stage_config.params: ddconfig, embed_dim, n_embed).  The
+    ldm_exp Encoder / Decoder normalise with 32 groups and eps 1e-6 (model.py:38-39)."""
+    if ddconfig.get('double_z', False):
+        raise NotImplementedError('double_z first stages are KL autoencoders, not VQ')
+    if list(ddconfig.get('attn_resolutions', [])):
+        raise NotImplementedError('attention inside the first stage\'s levels (attn_resolutions) is not a VQModel layout')
+    if ddconfig.get('attn_type', 'vanilla') != 'vanilla':
+        raise NotImplementedError('attn_type %r' % ddconfig.get('attn_type'))
+    mult = list(ddconfig['ch_mult'])
+    return dict(in_channels=ddconfig.get('in_channels', 3), out_channels=ddconfig.get('out_ch', 3),
+                down_block_types=['DownEncoderBlock2D'] * len(mult), up_block_types=['UpDecoderBlock2D'] * len(mult),
+                block_out_channels=[ddconfig['ch'] * m for m in mult], layers_per_block=ddconfig['num_res_blocks'], act_fn='silu',
+                latent_channels=ddconfig['z_channels'], sample_size=ddconfig.get('resolution', 256), num_vq_embeddings=n_embed,
+                norm_num_groups=32, vq_embed_dim=embed_dim, scaling_factor=0.18215)

@@ -389,3 +389,41 @@ class DDIMPipeline(_PipelineBase):
         finally:
             fwd.close()
         return _to_output(self, image, output_type, return_dict)
+
+
+class LDMPipeline(_PipelineBase):
+    """pipelines/latent_diffusion_uncond/pipeline_latent_diffusion_uncond.py:44-111: unconditional latent diffusion -- the
+    scheduler loop over the UNet's latents (the captured / pinned forward of `_sampling_forward`), then the VQ first stage's
+    decode (vq.VQModel) and the usual [0, 1] image output."""
+
+    def __init__(self, vqvae, unet, scheduler):
+        super().__init__(unet, scheduler)
+        self.vqvae = vqvae
+
+    def to(self, device):
+        self.unet.to(device)
+        self.vqvae.to(device)
+        return self
+
+    @torch.no_grad()
+    def __call__(self, batch_size=1, generator=None, eta=0.0, num_inference_steps=50, output_type='pil', return_dict=True,
+                 **kwargs):
+        import inspect
+        ss = self.unet.config.sample_size
+        shape = (batch_size, self.unet.config.in_channels, ss, ss)
+        latents = randn_tensor(shape, generator=generator)              # drawn on the host, as the reference does, then moved
+        latents = latents.to(self.device)
+        if self.scheduler.init_noise_sigma != 1.0:                    # (x 1.0 is the identity)
+            latents = latents * self.scheduler.init_noise_sigma
+        self.scheduler.set_timesteps(num_inference_steps)
+        extra = {'eta': eta} if 'eta' in inspect.signature(self.scheduler.step).parameters else {}
+        ts = [int(t) for t in self.scheduler.timesteps.tolist()]
+        fwd = _sampling_forward(self.unet, shape, len(ts))
+        try:
+            for t in self.progress_bar(ts):
+                noise_prediction = fwd(self.scheduler.scale_model_input(latents, t), t)
+                latents = self.scheduler.step(noise_prediction, t, latents, **extra).prev_sample
+        finally:
+            fwd.close()
+        image = self.vqvae.decode(latents).sample
+        return _to_output(self, image, output_type, return_dict)

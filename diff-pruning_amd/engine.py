@@ -579,6 +579,8 @@ class UNetEngine:
             o, c = self._temb[1][pre]
             tproj = self._temb[2][:xa.shape[0], o:o + c]   # column slice of the batched projection (row stride = sum C); the
                                                            # rows of this block's images (LdmEngine: shared CFG stem)
+        elif semb is None:
+            tproj = None                                   # no time embedding (the VQ autoencoder's blocks, temb_channels=None)
         else:
             tproj = self._linear(pre + nm['temb'], semb)
         h = self._conv(pre + nm['conv1'], n1, None, _SPEC3, tadd=tproj)
@@ -636,7 +638,8 @@ class UNetEngine:
         hd = self.cfg.get('attention_head_dim')
         return channels // hd if hd is not None else 1
 
-    def attn_fwd(self, pre, x, scale, rescale, save, heads=1):
+    def attn_fwd(self, pre, x, scale, rescale, save, heads=1, fused_attn=None):
+        """fused_attn: None = the ops.FUSED_ATTN rule; True / False force the one-kernel / three-launch form of a no-grad pass."""
         P, cfg = self.P, self.cfg
         G, eps = cfg['norm_num_groups'], cfg['norm_eps']
         N, C, H, W = x.shape
@@ -656,7 +659,11 @@ class UNetEngine:
         # contiguous channel rows [h*d, (h+1)*d) of every image -> batch index n*heads + h
         Z, d = N * heads, inner // heads
         vd = v.shape[1] // heads                      # the value width may differ from the query / key width after pruning
-        if save is None and getattr(ops, 'FUSED_ATTN', False) and ops.attention_fused_ok(T, d, vd):
+        if fused_attn is None:
+            one_kernel = save is None and getattr(ops, 'FUSED_ATTN', False) and ops.attention_fused_ok(T, d, vd)
+        else:
+            one_kernel = save is None and fused_attn and bool(ops._lib().dp_attention_fwd_supported(int(T), int(d), int(vd)))
+        if one_kernel:
             p = None                                  # sampling forward: one kernel, no [T, T] scores (csrc/attention.hip)
             o = ops.attention_fwd(q, k, v, heads, scale)
         else:

@@ -461,3 +461,15 @@ def ldm_importance_sweep(model, embedder, schedule=None, num_steps=1000, thr=0.1
         dist.all_reduce(flat, group=group)           # the one exchange step of the pass (sum of the per-shard gradients)
     return dict(losses=losses, steps=len(losses), accumulated=accumulated, flat_grads=flat, shard=(lo, hi),
                 global_batch=n_samples, sampler_rows=rows)
+
+
+@torch.no_grad()
+def decode_first_stage(vq, z, scale_factor=1.0, force_not_quantize=False):
+    """LatentDiffusion.decode_first_stage (ldm/models/diffusion/ddpm.py:706-761), the unsplit path with predict_cids=False:
+    z / scale_factor, then the VQ first stage's decode (ldm/models/autoencoder.py:274-283) -- quantize unless
+    force_not_quantize, post_quant_conv, decoder.  `vq`: a VQModel (vq.py), e.g. built from an ldm_exp first stage by
+    checkpoint.convert_ldm_first_stage / vq_config_from_ldm.  Returns images [N, 3, H, W] in the decoder's range."""
+    z = z.detach().to(torch.float32).contiguous()
+    if scale_factor != 1.0:
+        z = ops.axpby(z, float(1.0 / scale_factor), torch.empty_like(z), 0.0)     # `1. / self.scale_factor * z` in fp32
+    return vq.decode(z, force_not_quantize=force_not_quantize).sample

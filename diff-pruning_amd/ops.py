@@ -1427,6 +1427,36 @@ def mse_fwd_bwd(out, noise, gscale, loss_scale, want_grad=True, stop_state=None)
     return loss, dout
 
 
+VQ_MAX_DIM = 16
+
+
+def vq_quantize(z, codebook, want_indices=True, want_loss=True, beta=0.25):
+    """Nearest-codebook quantization of z [N, D, H, W] (channel-major; any image stride) against codebook [K, D]
+    (csrc/vq.hip; VectorQuantizer.forward, vae.py:332-364, legacy=True).  Returns (z_q [N, D, H, W], loss 0-d fp32 device tensor
+    = (1 + beta) * mean((e_idx - z)^2) or None, indices int64 [N * H * W] in (n, h, w) order or None).  Ties: the lowest index."""
+    if z.dim() == 4 and z.shape[1] > VQ_MAX_DIM:
+        raise NotImplementedError('vq_quantize: codebook vectors of %d channels (the kernel takes 1 ... %d)' % (z.shape[1], VQ_MAX_DIM))
+    _chk_act(z)
+    N, D, H, W = z.shape
+    assert codebook.dtype == _f32 and codebook.is_cuda and codebook.device == z.device and codebook.dim() == 2 \
+        and codebook.shape[1] == D and codebook.shape[0] >= 1, 'codebook must be an fp32 [K, %d] device tensor' % D
+    E = codebook.contiguous()
+    P = N * H * W
+    zq = empty_act((N, D, H, W), z.device)
+    idx = torch.empty(P, dtype=torch.int64, device=z.device) if want_indices else None
+    nb = max(int(_lib().dp_vq_blocks(P)), 1)
+    partial = torch.empty(nb, dtype=torch.float64, device=z.device) if want_loss else None
+    zbs = z.stride(0) if N > 1 else D * H * W
+    L.check(_lib().dp_vq_quantize(_p(z), zbs, D, H * W, P, _p(E), E.shape[0], _p(zq), D * H * W, _p(idx), _p(partial),
+                                  _stream()), 'dp_vq_quantize')
+    loss = None
+    if want_loss:
+        loss = torch.zeros((), dtype=_f32, device=z.device)
+        if P > 0:
+            L.check(_lib().dp_vq_loss(_p(partial), nb, (1.0 + float(beta)) / (P * D), _p(loss), _stream()), 'dp_vq_loss')
+    return zq, loss, idx
+
+
 def kd_fwd_bwd(out, teacher_out, noise, w_kd, w_eps, gscale, loss_scale, nblocks=MSE_BLOCKS):
     """Distillation loss (functions/losses.py:17-31) of the student output `out` against the frozen teacher's output and the noise.
     Returns (terms[3] device tensor = [w_kd * kd + w_eps * eps, kd, eps] with kd = loss_scale * sum (T - S)^2,

@@ -36,6 +36,14 @@ LDM_CIN256_CFG = dict(image_size=64, in_channels=3, out_channels=3, model_channe
 # same topology at reduced width / resolution for full-tensor fixtures
 LDM_TINY_CFG = dict(LDM_CIN256_CFG, image_size=16, model_channels=32, context_dim=16)
 
+# VQ-f4 first stage of cin256-v2.yaml:41-59 (ch 128, ch_mult (1, 2, 4), 2 res blocks, z 3, 8192 codes) as a Diffusers VQModel config
+VQ_F4_CFG = dict(in_channels=3, out_channels=3, down_block_types=['DownEncoderBlock2D'] * 3, up_block_types=['UpDecoderBlock2D'] * 3,
+                 block_out_channels=[128, 256, 512], layers_per_block=2, act_fn='silu', latent_channels=3, sample_size=256,
+                 num_vq_embeddings=8192, norm_num_groups=32, vq_embed_dim=3, scaling_factor=0.18215)
+# reduced width for full-tensor fixtures (125 state-dict keys)
+VQ_TINY_CFG = dict(VQ_F4_CFG, down_block_types=['DownEncoderBlock2D'] * 2, up_block_types=['UpDecoderBlock2D'] * 2,
+                   block_out_channels=[32, 64], layers_per_block=1, sample_size=16, num_vq_embeddings=64, norm_num_groups=8)
+
 
 def _rng(name, seed):
     return np.random.default_rng([zlib.crc32(name.encode()), seed])

@@ -432,6 +432,18 @@ int dp_mse_per_image(const float* a, const float* b, int N, long long per, float
 int dp_u8_to_float(const unsigned char* src, int hwc, int N, int C, int H, int W, float* out, long long out_img_stride,
                    int mode, unsigned flip_thr24, int dequant, const dp_dropout* rng, void* stream);
 
+/* Nearest-codebook vector quantizer (csrc/vq.hip; diffusers VectorQuantizer.forward, vae.py:332-364, legacy=True, remap=None).
+ * z [N][D][H][W] channel-major (image stride z_bs floats, HW = H * W, P = N * HW pixels), codebook E [K][D] row-major.
+ * idx[p] = argmin_k sum_d (z[p,d] - E[k,d])^2 in the direct form, the lowest k among equal fp32 distances;
+ * zq[p,d] = z[p,d] + (E[idx,d] - z[p,d]) in two fp32 roundings (image stride zq_bs); idx (int64 [P]) and partial (fp64
+ * [dp_vq_blocks(P)]: per-block sums of (E[idx,d] - z[p,d])^2) may be NULL.  1 <= D <= 16 (else hipErrorNotSupported), K >= 1.
+ * dp_vq_loss: loss[0] = (float)(scale * sum of the partials) in a fixed order -- (1 + beta) / (P * D) gives the reference's
+ * mean + beta * mean.  Plain vector stores, no atomics: deterministic. */
+int dp_vq_blocks(long long P);
+int dp_vq_quantize(const float* z, long long z_bs, int D, int HW, long long P, const float* E, int K, float* zq, long long zq_bs,
+                   long long* idx, double* partial, void* stream);
+int dp_vq_loss(const double* partial, int nblocks, double scale, float* loss, void* stream);
+
 /* Native replay list (csrc/replay.hip): re-issue the kernels / memsets of a stream-captured step from a C loop.  The
  * reference's loop re-launches ~700 ATen kernels per timestep from Python (ddpm_prune.py:94-106); here one timestep is captured
  * once into a hipGraph (never instantiated: hipGraphLaunch of these graphs costs more host time than eager launches on this
