@@ -459,3 +459,81 @@ def vq_config_from_ldm(ddconfig, embed_dim, n_embed):
                 block_out_channels=[ddconfig['ch'] * m for m in mult], layers_per_block=ddconfig['num_res_blocks'], act_fn='silu',
                 latent_channels=ddconfig['z_channels'], sample_size=ddconfig.get('resolution', 256), num_vq_embeddings=n_embed,
                 norm_num_groups=32, vq_embed_dim=embed_dim, scaling_factor=0.18215)
+
+
+# --------------------------------------------------------------------------------------------------------
+# finetuned LDM weights in the reference's LatentDiffusion key layout (ldm_exp/main.py checkpoints, read back by
+# sample_for_FID.py:44-48 with `load_state_dict(sd, strict=False)` into the pruned pickle)
+# --------------------------------------------------------------------------------------------------------
+LDM_UNET_PREFIX, LDM_EMBEDDER_PREFIX, LDM_EMA_PREFIX = 'model.diffusion_model.', 'cond_stage_model.', 'model_ema.'
+
+
+def lit_ema_key(name):
+    """LitEma's buffer name of UNet parameter `name` (ldm/modules/ema.py:16-21: the DiffusionWrapper's parameter name
+    'diffusion_model.<name>' with every dot removed, since buffer names may not contain dots)."""
+    return LDM_EMA_PREFIX + ('diffusion_model.' + name).replace('.', '')
+
+
+def _ema_parts(ema):
+    if ema is None:
+        return None
+    if isinstance(ema, dict):
+        return float(ema['decay']), int(ema['num_updates']), ema['shadow']
+    return float(ema.ema_decay), int(ema.num_updates), ema.ema_state()       # an ldm_train.LdmFinetuneEngine
+
+
+def ldm_finetuned_state_dict(model, embedder, ema=None):
+    """{'model.diffusion_model.<name>', 'cond_stage_model.embedding.weight', and with `ema` 'model_ema.decay',
+    'model_ema.num_updates', 'model_ema.diffusion_model<name without dots>'} -> CPU tensors.
+    ema: None, an ldm_train.LdmFinetuneEngine built with use_ema=True, or dict(decay, num_updates, shadow={name: tensor})."""
+    sd = {LDM_UNET_PREFIX + n: p.detach().cpu().clone() for n, p in model.named_parameters()}
+    sd.update({LDM_EMBEDDER_PREFIX + n: p.detach().cpu().clone() for n, p in embedder.named_parameters()})
+    parts = _ema_parts(ema)
+    if parts is not None:
+        decay, num_updates, shadow = parts
+        sd[LDM_EMA_PREFIX + 'decay'] = torch.tensor(decay, dtype=torch.float32)
+        sd[LDM_EMA_PREFIX + 'num_updates'] = torch.tensor(num_updates, dtype=torch.int)
+        for n, _ in model.named_parameters():
+            sd[lit_ema_key(n)] = shadow[n].detach().cpu().clone()
+    return sd
+
+
+def save_ldm_finetuned(path, model, embedder, ema=None):
+    """A file holding {'state_dict': ldm_finetuned_state_dict(...)}, the layout of the reference's Lightning checkpoints."""
+    torch.save({'state_dict': ldm_finetuned_state_dict(model, embedder, ema)}, path)
+
+
+def load_ldm_finetuned(path, model, embedder):
+    """Load a save_ldm_finetuned file (or a reference checkpoint of the same, possibly pruned, shapes) into `model` and
+    `embedder` in place (parameters that live in a finetune engine's flat buffer stay there).  Keys this package does not know
+    (`first_stage_model.*`, `betas`, ...) are ignored, as under strict=False; a key it knows with another shape is an error.
+    Returns dict(missing=[keys of ours absent from the file], ema=None | dict(decay, num_updates, shadow={name: tensor}))."""
+    blob = torch.load(os.fspath(path), map_location='cpu', weights_only=True) if isinstance(path, (str, os.PathLike)) else path
+    sd = blob['state_dict'] if 'state_dict' in blob else blob
+    missing = []
+    with torch.no_grad():
+        for prefix, mod in ((LDM_UNET_PREFIX, model), (LDM_EMBEDDER_PREFIX, embedder)):
+            for n, p in list(mod.named_parameters()) + list(mod.named_buffers()):
+                t = sd.get(prefix + n)
+                if t is None:
+                    missing.append(prefix + n)
+                    continue
+                if tuple(t.shape) != tuple(p.shape):
+                    raise ValueError('%s: checkpoint shape %s, model shape %s' % (prefix + n, tuple(t.shape), tuple(p.shape)))
+                p.data.copy_(t)
+    eng = getattr(model, '_engine', None)
+    if eng is not None:
+        eng.packs.clear()                                   # in-place weight writes are invisible to the pack cache
+    ema = None
+    if LDM_EMA_PREFIX + 'decay' in sd:
+        shadow = {}
+        for n, p in model.named_parameters():
+            t = sd.get(lit_ema_key(n))
+            if t is None:
+                missing.append(lit_ema_key(n))
+            elif tuple(t.shape) != tuple(p.shape):
+                raise ValueError('%s: checkpoint shape %s, model shape %s' % (lit_ema_key(n), tuple(t.shape), tuple(p.shape)))
+            else:
+                shadow[n] = t
+        ema = dict(decay=float(sd[LDM_EMA_PREFIX + 'decay']), num_updates=int(sd[LDM_EMA_PREFIX + 'num_updates']), shadow=shadow)
+    return dict(missing=missing, ema=ema)

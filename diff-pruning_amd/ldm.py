@@ -379,11 +379,13 @@ class LdmEngine(UNetEngine):
             rows = ops.rowsum_nc(dh2)
             dv2 = self._linear_bwd(tb + '.attn2.to_out.0', rows, v2)
             self._linear_bwd(tb + '.attn2.to_v', dv2, ctx2d, need_dx=False)
+            if self._dctx is not None:                 # d context[n] = sum over blocks of dv2[n] @ W_v: ONE launch after the pass
+                self._dctx[2].append((tb + '.attn2.to_v.weight', dv2))
             dh1 = dh2                                  # h2 = h1 + (a row vector that does not depend on h1)
         else:
             # attn2 over L > 1 context tokens: the self-attention backward with K, V projected from the context; norm2 / to_q get
-            # gradients now (over a single key the softmax is constant and they are exactly zero), the context itself gets none
-            # (the importance pass differentiates the UNet's parameters only)
+            # gradients now (over a single key the softmax is constant and they are exactly zero); the context itself gets one
+            # only when backward(want_context_grad=True) asks (the importance pass differentiates the UNet's parameters only)
             l2, ls2, q2, k2, p2, o2, cx = x2
             a2, b2, L_ = q2.shape[1], v2.shape[1], cx.shape[3]
             do2 = self._conv_bwd(tb + '.attn2.to_out.0', dh2, o2.view(N, b2, H, W), None, _SPEC1, hw)
@@ -393,8 +395,15 @@ class LdmEngine(UNetEngine):
             ds2 = ops.softmax_bwd(p2, dp2, scale, out=dp2)
             dq2 = ops.bmm_nt(k2.view(Z, a2 // heads, L_), ds2)                 # [Z, d, T]
             dk2 = ops.bmm_nn(q2.view(Z, a2 // heads, T), ds2)                  # [Z, d, L]
-            self._conv_bwd(tb + '.attn2.to_k', dk2.view(N, a2, 1, L_), cx, None, _SPEC1, (1, L_), need_dx=False)
-            self._conv_bwd(tb + '.attn2.to_v', dv2.view(N, b2, 1, L_), cx, None, _SPEC1, (1, L_), need_dx=False)
+            if self._dctx is None:
+                self._conv_bwd(tb + '.attn2.to_k', dk2.view(N, a2, 1, L_), cx, None, _SPEC1, (1, L_), need_dx=False)
+                self._conv_bwd(tb + '.attn2.to_v', dv2.view(N, b2, 1, L_), cx, None, _SPEC1, (1, L_), need_dx=False)
+            else:                                      # input gradients of the two context projections, summed into [N, D, 1, L]
+                self._conv_bwd(tb + '.attn2.to_k', dk2.view(N, a2, 1, L_), cx, None, _SPEC1, (1, L_), dx_out=self._dctx[0],
+                               dx_accumulate=self._dctx[1])
+                self._conv_bwd(tb + '.attn2.to_v', dv2.view(N, b2, 1, L_), cx, None, _SPEC1, (1, L_), dx_out=self._dctx[0],
+                               dx_accumulate=True)
+                self._dctx[1] = True
             dl2 = self._conv_bwd(tb + '.attn2.to_q', dq2.view(N, a2, H, W), l2, None, _SPEC1, hw)
             dh1, pws2 = ops.layernorm_bwd(h1, P[tb + '.norm2.weight'], ls2, dl2, add=dh2)
             self._ln_param_grads(tb + '.norm2', pws2)
@@ -447,6 +456,7 @@ class LdmEngine(UNetEngine):
             raise NotImplementedError('context must be [B, L, context_dim] (cin256-v2: the one class-embedding token, L = 1)')
         if cfg_pair and (save or context.shape[0] != 2 * x.shape[0]):
             raise ValueError('cfg_pair: a no-grad forward of B images against 2B context tokens')
+        self._ctx_shape = tuple(context.shape)
         if context.shape[1] == 1:                      # every configuration the reference prunes: the closed form of st_fwd
             ctx2d = context.reshape(context.shape[0], context.shape[2]).contiguous().float()
         else:                                          # L > 1 tokens: [B, L, D] -> channel-major [B, D, 1, L] for the 1x1 projections
@@ -532,9 +542,39 @@ class LdmEngine(UNetEngine):
             self.ctx = ctx
         return y
 
-    def backward(self, dout):
+    _dctx = None          # [accumulator, written?, [(W_v name, dv2)]] of the context gradient while backward(want_context_grad=True) runs
+
+    def backward(self, dout, want_context_grad=False):
+        """Parameter gradients into the bound buffers.  want_context_grad=True also returns d loss / d context [N, L, D] (the
+        finetune step trains the class embedder with the UNet, ddpm.py:1372-1377): per transformer block the input gradient of
+        attn2.to_v (L = 1: the closed form has no other path to the context; all blocks in one launch after the pass) or of
+        attn2.to_k and attn2.to_v (L > 1, accumulated in block order of the backward pass).  Off (the default), the pass launches
+        exactly what it did without the switch."""
         P, cfg, ctx = self.P, self.cfg, self.ctx
         assert ctx is not None
+        if want_context_grad:
+            cshape = getattr(self, '_ctx_shape', None)
+            assert cshape is not None
+            n_, l_, d_ = cshape
+            acc = torch.empty((n_, d_) if l_ == 1 else (n_, d_, 1, l_), dtype=torch.float32, device=dout.device)
+            self._dctx = [acc, False, []]
+        try:
+            self._backward(dout)
+            if not want_context_grad:
+                return None
+            acc, written, parts = self._dctx
+            if parts:
+                # L = 1: the dv2 of every transformer block side by side ([N, sum inner]; cin256-v2: 10 560 columns un-pruned) against
+                # the stacked W_v -- one M = N contraction instead of sixteen
+                acc = ops.linear_dgrad(torch.cat([dv for _, dv in parts], 1), torch.cat([P[n] for n, _ in parts], 0))
+            elif not written:                        # a network without a SpatialTransformer
+                acc.zero_()
+            return acc.view(acc.shape[0], 1, acc.shape[1]) if acc.dim() == 2 else acc.view(acc.shape[0], acc.shape[1], acc.shape[3]).transpose(1, 2).contiguous()
+        finally:
+            self._dctx = None
+
+    def _backward(self, dout):
+        P, cfg, ctx = self.P, self.cfg, self.ctx
         inp, out, mid = ldm_blocks(cfg)
         x, t_emb, h1, a1, emb, semb, ho, no, sto = ctx.pop('_head')
         self._begin_backward()

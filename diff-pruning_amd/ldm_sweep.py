@@ -473,3 +473,14 @@ def decode_first_stage(vq, z, scale_factor=1.0, force_not_quantize=False):
     if scale_factor != 1.0:
         z = ops.axpby(z, float(1.0 / scale_factor), torch.empty_like(z), 0.0)     # `1. / self.scale_factor * z` in fp32
     return vq.decode(z, force_not_quantize=force_not_quantize).sample
+
+
+@torch.no_grad()
+def encode_first_stage(vq, images, scale_factor=1.0):
+    """LatentDiffusion.encode_first_stage + get_first_stage_encoding (ldm/models/diffusion/ddpm.py:826-863, 542-551) for the VQ
+    first stage: VQModelInterface.encode -- encoder, quant_conv, NO quantisation -- times scale_factor.  `vq`: a VQModel (vq.py).
+    Returns the latents [N, z, H / f, W / f] the finetune step diffuses (ldm_train.LdmFinetuneEngine.step_images)."""
+    z = vq.encode(images).latents
+    if scale_factor != 1.0:
+        z = ops.axpby(z.contiguous(), float(scale_factor), torch.empty_like(z), 0.0)      # `self.scale_factor * z` in fp32
+    return z

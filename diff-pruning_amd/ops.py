@@ -1605,6 +1605,51 @@ def adam_ema_dev(p_, g, m, v, ema, coef, hyper, b1, b2, eps, ema_decay):
                                    _stream()), 'dp_adam_ema_dev')
 
 
+def adamw_scalars(lr, b1, b2, wd, step):
+    """The by-value scalars of dp_adamw_ema as torch.optim.AdamW forms them: Python doubles, rounded to fp32 once by the call."""
+    bc1 = 1.0 - b1 ** step
+    bc2 = 1.0 - b2 ** step
+    return dict(p_scale=1.0 - lr * wd, one_minus_b1=1.0 - b1, b2=b2, one_minus_b2=1.0 - b2, sqrt_bc2=bc2 ** 0.5,
+                step_size=lr / bc1)
+
+
+def adamw_ema(p_, g, m, v, ema, lr, b1, b2, eps, weight_decay, step, ema_decay=0.0, coef=None):
+    """One torch.optim.AdamW step (decoupled weight decay) over flat fp32 buffers; with `ema` (LitEma shadow) also
+    `ema -= (1 - ema_decay) * (ema - p)`, ema_decay = the decay in force at this update (ldm_train.lit_ema_decay)."""
+    n = p_.numel()
+    for t in (p_, g, m, v) + ((ema,) if ema is not None else ()):
+        assert t.is_cuda and t.dtype == _f32 and t.is_contiguous() and t.numel() == n, 'adamw_ema: flat contiguous fp32 device buffers'
+    s = adamw_scalars(lr, b1, b2, weight_decay, step)
+    L.check(_lib().dp_adamw_ema(_p(p_), _p(g), _p(m), _p(v), _p(ema), n, _p(coef), s['p_scale'], s['one_minus_b1'], s['b2'],
+                                s['one_minus_b2'], s['sqrt_bc2'], eps, s['step_size'], float(ema_decay), _stream()), 'dp_adamw_ema')
+
+
+EMBEDDING_BWD_MAX_ROWS = 4096
+
+
+def check_class_ids(ids, n_classes):
+    """Host-side range check of the ids an embedding kernel will index with (a ValueError, never a device fault)."""
+    ids = torch.as_tensor(ids)
+    if ids.dtype not in (torch.int64, torch.int32) or ids.dim() != 1:
+        raise ValueError('class ids must be a 1-D integer tensor, got %s %s' % (ids.dtype, tuple(ids.shape)))
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_classes):
+        raise ValueError('class ids must lie in [0, %d): got %d .. %d' % (n_classes, int(ids.min()), int(ids.max())))
+    return ids.to(torch.int64)
+
+
+def embedding_bwd(ids_dev, dctx, dW):
+    """dW[ids[b], :] += dctx[b, :], repeated ids added in ascending b (bitwise reproducible).  `ids_dev`: int64 device tensor whose
+    range the caller has checked on the host (check_class_ids) -- the kernel does not."""
+    B, D = dctx.shape
+    assert ids_dev.dtype == torch.int64 and ids_dev.is_cuda and ids_dev.numel() == B and ids_dev.is_contiguous()
+    assert dctx.is_cuda and dctx.dtype == _f32 and dctx.is_contiguous() and dW.is_cuda and dW.dtype == _f32 and dW.is_contiguous()
+    assert dW.dim() == 2 and dW.shape[1] == D
+    if B > EMBEDDING_BWD_MAX_ROWS:
+        raise ValueError('embedding_bwd: at most %d rows per call, got %d' % (EMBEDDING_BWD_MAX_ROWS, B))
+    L.check(_lib().dp_embedding_bwd(_p(ids_dev), _p(dctx), B, D, _p(dW), _stream()), 'dp_embedding_bwd')
+    return dW
+
+
 def ddim_step(x, eps, a_t, a_prev, std=0.0, vnoise=None, clip=True, out=None, clip_range=1.0):
     if out is None:
         out = torch.empty_like(x)

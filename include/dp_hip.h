@@ -377,6 +377,19 @@ int dp_clip_coef(const float* partial, int n, float max_norm, float* norm_out, f
 int dp_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* clip_coef,
                 float lr, float b1, float b2, float eps, float bc1, float bc2, float ema_decay, void* stream);
 
+/* LDM finetune update (ldm_exp/ldm/models/diffusion/ddpm.py:1372-1381; ldm/modules/ema.py) over flat buffers, one pass:
+ *   torch.optim.AdamW, single tensor, in torch's order:  p *= p_scale (= 1 - lr wd);  m += (g - m) one_minus_b1;
+ *   v = b2 v + one_minus_b2 g g;  p -= step_size (= lr / bc1) * m / (sqrt(v) / sqrt_bc2 + eps);
+ *   then iff ema != NULL LitEma's  s -= (1 - ema_decay) (s - p).  Every scalar is formed by the host in double and rounded to
+ *   fp32 once (ema_decay: LitEma's fp32 decay after warm-up).  clip_coef: NULL, or a device scalar the gradient is scaled by.
+ *   16-byte accesses when all buffers are 16-byte aligned, 4-byte accesses for the n % 4 tail; any n (long long indexing). */
+int dp_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* clip_coef,
+                 float p_scale, float one_minus_b1, float b2, float one_minus_b2, float sqrt_bc2, float eps,
+                 float step_size, float ema_decay, void* stream);
+/* Gradient of an embedding lookup: dW[ids[b], :] += dctx[b, :] for b = 0 .. B-1 (B <= 4096), the rows of a repeated id added in
+ * ascending b -- bitwise reproducible, no float atomics.  ids: int64, every id in [0, rows of dW) (checked by the caller). */
+int dp_embedding_bwd(const long long* ids, const float* dctx, int B, int D, float* dW, void* stream);
+
 /* DDIM update (scheduling_ddim.py:324-370, eta = 0 or with supplied noise):
  *   x0 = clamp((x - sqrt(1-a_t) eps)/sqrt(a_t), +-clip_range);  prev = sqrt(a_prev) x0 + sqrt(1-a_prev-std^2) eps (+ std*noise) */
 int dp_ddim_step(const float* x, const float* eps, const float* vnoise, float a_t, float a_prev, float std, int clip,
