@@ -176,6 +176,7 @@ SIGNATURES = {
     'dp_replay_free': [_vp],
     'dp_version': [],
     'dp_launch_count': [],
+    'dp_recent_launches': [C.POINTER(C.c_char_p), _i],
 }
 
 _lib = None

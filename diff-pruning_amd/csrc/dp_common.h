@@ -137,6 +137,12 @@ static inline DpDrop dp_drop_host(const dp_dropout* d) {
 }
 
 #define DP_LAUNCH_CHECK() ((int)hipGetLastError())
-// every kernel launch of the library goes through DP_LAUNCH: dp_launch_count() reports launches per step in bench.py
+// every kernel launch of the library goes through DP_LAUNCH: dp_launch_count() reports launches per step in bench.py, and the
+// stringised kernel expression of each launch is kept in a host-side ring of DP_LAUNCH_RING entries (dp_recent_launches(), so
+// that a test can see which kernel / template instantiation a launcher chose).  Host only: one pointer store (to a string
+// literal) and one increment per launch, no allocation, no synchronisation, nothing on the device, safe during stream
+// capture.  Like dp_launches it is NOT thread-safe: launches from two host threads at once may lose a count or a name.
+#define DP_LAUNCH_RING 256
 extern unsigned long long dp_launches;
-#define DP_LAUNCH(...) do { ++dp_launches; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+extern const char* dp_launch_names[DP_LAUNCH_RING];
+#define DP_LAUNCH(k, ...) do { dp_launch_names[dp_launches++ & (DP_LAUNCH_RING - 1)] = #k; hipLaunchKernelGGL(k, __VA_ARGS__); } while (0)

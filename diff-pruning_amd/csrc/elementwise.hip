@@ -4,7 +4,15 @@
 #include "dp_common.h"
 
 unsigned long long dp_launches = 0;
+const char* dp_launch_names[DP_LAUNCH_RING] = {};
 extern "C" long long dp_launch_count(void) { return (long long)dp_launches; }
+extern "C" int dp_recent_launches(const char** out, int cap) {
+    unsigned long long have = dp_launches < DP_LAUNCH_RING ? dp_launches : DP_LAUNCH_RING;
+    if (cap < 0) cap = 0;
+    if (have > (unsigned long long)cap) have = (unsigned long long)cap;
+    for (unsigned long long i = 0; i < have; ++i) out[i] = dp_launch_names[(dp_launches - have + i) & (DP_LAUNCH_RING - 1)];
+    return (int)have;
+}
 
 static inline unsigned dp_grid(long long n, int per_block = 256, unsigned cap = 8192) {
     long long nb = (n + per_block - 1) / per_block;

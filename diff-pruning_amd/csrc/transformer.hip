@@ -8,7 +8,11 @@
 // Workgroup = 64 consecutive tokens x 4 channel groups (wavefront w walks channels w, w+4, ...): every access is a
 // contiguous 256-byte run of tokens, the channel loop is 4x shorter and carries two independent load streams per lane
 // (one thread per token with 3 serial passes over up to 960 channels was latency bound: 31 % of an LDM step).
-// Variance in one pass around the token's first channel as the shift (stable: the shifted mean is small).
+// Two passes over the token's channels, both in a fixed summation order: the mean first (summed around the token's first channel
+// as the shift, so that a large common offset costs no bits), then the variance as the mean of (x - mean)^2.  The squares are
+// taken of the centred values, so no input cancels: an outlier in any channel (the shift channel included) or an offset of
+// 30 sigma leaves y within a few fp32 roundings of the fp64 result.  (The earlier single pass, var = E[(x - x0)^2] - (mean - x0)^2,
+// lost eps * (mean - x0)^2 / var: 5e-5 .. 2e-4 of max|y| when channel 0 was an outlier.)
 // TOK tokens x (256 / TOK) channel groups per workgroup: 64 x 4 for large token counts; 16 x 16 when 64-token workgroups would
 // leave the chip mostly idle (LDM importance pass: 6 latents x 1024 tokens = 96 workgroups on 256 CUs; 161 us for 28 MB).
 template <int TOK>
@@ -26,23 +30,32 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     const int t = (int)(tk - (long long)n * T);
     const float* xp = x + (long long)n * x_img_stride + t;
     const float k = xp[0];
-    float s0 = 0.f, s1 = 0.f, q0 = 0.f, q1 = 0.f;
+    float s0 = 0.f, s1 = 0.f;
     int c = cg;
     for (; c + CG < C; c += 2 * CG) {
-        const float v0 = xp[(long long)c * T] - k, v1 = xp[(long long)(c + CG) * T] - k;
-        s0 += v0; q0 += v0 * v0;
-        s1 += v1; q1 += v1 * v1;
+        s0 += xp[(long long)c * T] - k;
+        s1 += xp[(long long)(c + CG) * T] - k;
     }
-    if (c < C) { const float v0 = xp[(long long)c * T] - k; s0 += v0; q0 += v0 * v0; }
+    if (c < C) s0 += xp[(long long)c * T] - k;
     r1[cg][tl] = s0 + s1;
+    __syncthreads();
+    float rs = 0.f;
+#pragma unroll
+    for (int j = 0; j < CG; ++j) rs += r1[j][tl];                                  // fixed order
+    const float mean = k + rs / (float)C;
+    float q0 = 0.f, q1 = 0.f;
+    for (c = cg; c + CG < C; c += 2 * CG) {
+        const float v0 = xp[(long long)c * T] - mean, v1 = xp[(long long)(c + CG) * T] - mean;
+        q0 += v0 * v0;
+        q1 += v1 * v1;
+    }
+    if (c < C) { const float v0 = xp[(long long)c * T] - mean; q0 += v0 * v0; }
     r2[cg][tl] = q0 + q1;
     __syncthreads();
-    float rs = 0.f, rq = 0.f;
+    float rq = 0.f;
 #pragma unroll
-    for (int j = 0; j < CG; ++j) { rs += r1[j][tl]; rq += r2[j][tl]; }            // fixed order
-    const float ms = rs / (float)C;
-    const float var = fmaxf(rq / (float)C - ms * ms, 0.f);
-    const float mean = k + ms;
+    for (int j = 0; j < CG; ++j) rq += r2[j][tl];                                  // fixed order
+    const float var = rq / (float)C;
     const float rstd = 1.0f / sqrtf(var + eps);
     if (!valid) return;
     if (cg == 0) {

@@ -481,6 +481,12 @@ int dp_version(void);
 /* Number of kernel launches this library has issued since it was loaded (host counter; bench.py reports launches per step).
  * Returned in place of an error code. */
 long long dp_launch_count(void);
+/* Names of the most recent kernel launches, oldest first: writes min(cap, launches so far, 256) pointers to static strings (the
+ * kernel expression of the launch site with its template arguments, e.g. "(gn_bwd_wave_kernel<8, false, false>)",
+ * "rowsum_kernel<true>") into out and returns how many.  With dp_launch_count() before and after a call, the last (after - before)
+ * names are the launches of that call.  Host-side ring next to the counter; like the counter it is not thread-safe.
+ * Returned in place of an error code. */
+int dp_recent_launches(const char** out, int cap);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,29 @@ def test_library_exports_every_declared_symbol():
     # struct sizes agree with the C header layout (all-int/pointer/long long members, natural alignment)
     assert ctypes.sizeof(L.ConvGeom) == 14 * 4 + 2 * 8
     assert ctypes.sizeof(L.Dropout) == 40 and lib.dp_launch_count() >= 0
+    names = (ctypes.c_char_p * 8)()
+    assert 0 <= lib.dp_recent_launches(names, 8) <= min(8, lib.dp_launch_count()) and lib.dp_recent_launches(names, 0) == 0
+
+
+def test_every_launch_site_of_the_tabled_files_is_in_the_branch_table():
+    """tests/test_dispatch_parity_gpu.py compares every dispatch branch of these files with fp64.  A new DP_LAUNCH site changes the
+    count recorded there, a new kernel name is in none of its tables: either fails here, before a GPU is needed, so the table
+    is edited (and a case written) together with the launcher."""
+    import test_dispatch_parity_gpu as D
+    csrc = os.path.join(ROOT, 'diff-pruning_amd', 'csrc')
+    tabled = {e.split(' | ')[0].split('<')[0] for e in D.BRANCHES}
+    assert not set(D.UNREACHED) - set(D.BRANCHES)
+    seen = set()
+    for fname, want in D.LAUNCH_SITES.items():
+        src = open(os.path.join(csrc, fname)).read()
+        sites = re.findall(r'\bDP_LAUNCH\(\(?\s*([A-Za-z_]\w*)', src)
+        assert len(sites) == want == src.count('DP_LAUNCH('), (fname, len(sites), want)
+        seen |= set(sites)
+    assert seen == tabled, (sorted(seen - tabled), sorted(tabled - seen))
+    assert all(e in D.CASES or e in D.UNREACHED for e in D.BRANCHES) and not set(D.CASES) & set(D.UNREACHED)
+    # the ring records the kernel expression of the launch site: its first macro argument, stringised
+    hdr = open(os.path.join(csrc, 'dp_common.h')).read()
+    assert re.search(r'#define DP_LAUNCH\(k, \.\.\.\).*= #k;.*hipLaunchKernelGGL\(k, __VA_ARGS__\)', hdr)
 
 
 def test_diffusers_pipeline_directory_io(tmp_path):

@@ -221,7 +221,8 @@ def test_bmm_variants(ops, report, Z, M, K, N):
 @pytest.mark.parametrize('N,C1,C2,H,G,silu', [(40, 256, 0, 8, 32, True), (33, 128, 128, 16, 32, False), (64, 512, 0, 4, 32, True),
                                               (2, 32, 0, 8, 8, True), (3, 128, 0, 32, 32, True), (2, 100, 92, 4, 32, True),
                                              (2, 64, 0, 16, 32, False), (1, 128, 0, 128, 32, True), (2, 32, 0, 3, 8, True),
-                                             (2, 48, 80, 64, 16, True), (1, 20, 44, 32, 8, True), (2, 64, 0, 256, 32, False), (2, 128, 128, 32, 32, True)])
+                                             (2, 48, 80, 64, 16, True), (1, 20, 44, 32, 8, True), (2, 64, 0, 256, 32, False), (2, 128, 128, 32, 32, True),
+                                             (32, 128, 0, 16, 32, True)])      # 4 channels x 256 pixels per group in 1024 groups: the 4-step wave kernels
 def test_groupnorm(ops, report, N, C1, C2, H, G, silu):
     xa = rnd(N, C1, H, H, seed=1) + 0.3
     xb = rnd(N, C2, H, H, seed=2) if C2 else None
@@ -468,7 +469,7 @@ def test_mse_wg_adam_ddim(ops, report):
     assert max(res.values()) < 1e-5, res
 
 
-@pytest.mark.parametrize('N,C,H', [(2, 96, 8), (3, 384, 16), (2, 50, 3)])
+@pytest.mark.parametrize('N,C,H', [(2, 96, 8), (3, 384, 16), (2, 50, 3), (4, 50, 128)])      # the last: N*T = 65536, the 64-token LayerNorm kernels
 def test_layernorm_geglu_rowvec(ops, report, N, C, H):
     x = rnd(N, C, H, H, seed=1) + 0.2
     gamma = 1 + 0.2 * rnd(C, seed=2)
