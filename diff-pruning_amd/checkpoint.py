@@ -498,18 +498,38 @@ def ldm_finetuned_state_dict(model, embedder, ema=None):
     return sd
 
 
-def save_ldm_finetuned(path, model, embedder, ema=None):
-    """A file holding {'state_dict': ldm_finetuned_state_dict(...)}, the layout of the reference's Lightning checkpoints."""
-    torch.save({'state_dict': ldm_finetuned_state_dict(model, embedder, ema)}, path)
+def save_ldm_finetuned(path, model, embedder, ema=None, training_state=None, epoch=0):
+    """A file holding {'state_dict': ldm_finetuned_state_dict(...)}, the layout of the reference's Lightning checkpoints.
+    training_state: an ldm_train.LdmFinetuneEngine -- adds what Lightning's `last.ckpt` carries to continue a run:
+    `optimizer_states` = [engine.optimizer_state_dict()] (torch.optim.AdamW's layout, UNet then embedder, ddpm.py:1372-1381),
+    `global_step` (optimizer steps) and `epoch`.  Lightning is not available to this project's tests, so these three container key
+    names are UNPINNED; the payload (AdamW's state layout) is pinned against torch itself."""
+    blob = {'state_dict': ldm_finetuned_state_dict(model, embedder, ema)}
+    if training_state is not None:
+        blob.update(optimizer_states=[training_state.optimizer_state_dict()], global_step=int(training_state.step_count),
+                    epoch=int(epoch))
+    torch.save(blob, path)
 
 
-def load_ldm_finetuned(path, model, embedder):
+def load_ldm_finetuned(path, model, embedder, engine=None):
     """Load a save_ldm_finetuned file (or a reference checkpoint of the same, possibly pruned, shapes) into `model` and
     `embedder` in place (parameters that live in a finetune engine's flat buffer stay there).  Keys this package does not know
     (`first_stage_model.*`, `betas`, ...) are ignored, as under strict=False; a key it knows with another shape is an error.
+    engine: the ldm_train.LdmFinetuneEngine of `model` and `embedder` -- also restores Adam's moments and step from
+    `optimizer_states[0]` and, when the engine keeps one, the LitEma shadow and `num_updates` (ValueError when the file has
+    none, raised before anything is written; an engine built with use_ema=False ignores a file's shadow); the hyper-parameters
+    stay the engine's.  The result then carries `global_step` and `epoch`.
     Returns dict(missing=[keys of ours absent from the file], ema=None | dict(decay, num_updates, shadow={name: tensor}))."""
     blob = torch.load(os.fspath(path), map_location='cpu', weights_only=True) if isinstance(path, (str, os.PathLike)) else path
     sd = blob['state_dict'] if 'state_dict' in blob else blob
+    if engine is not None:                                  # what can be refused is refused before the first write
+        if engine.model is not model or engine.embedder is not embedder:
+            raise ValueError('load_ldm_finetuned: `engine` does not train this model and embedder')
+        if 'optimizer_states' not in blob:
+            raise ValueError('load_ldm_finetuned(engine=...): the file holds no optimizer_states (written without training_state=)')
+        if engine.ema is not None and LDM_EMA_PREFIX + 'decay' not in sd:
+            raise ValueError('the engine keeps a LitEma shadow, the file has none (model_ema.*): a resumed run would go on '
+                             'with a stale shadow')
     missing = []
     with torch.no_grad():
         for prefix, mod in ((LDM_UNET_PREFIX, model), (LDM_EMBEDDER_PREFIX, embedder)):
@@ -536,4 +556,222 @@ def load_ldm_finetuned(path, model, embedder):
             else:
                 shadow[n] = t
         ema = dict(decay=float(sd[LDM_EMA_PREFIX + 'decay']), num_updates=int(sd[LDM_EMA_PREFIX + 'num_updates']), shadow=shadow)
-    return dict(missing=missing, ema=ema)
+    out = dict(missing=missing, ema=ema)
+    if engine is not None:
+        own = None
+        if engine.ema is not None:
+            own = engine.ema_state()
+            absent = [n for n in own if n not in ema['shadow']]
+            if absent:
+                raise ValueError('the file\'s LitEma shadow lacks %s' % absent[:5])
+        engine.load_optimizer_state_dict(blob['optimizer_states'][0])
+        if own is not None:
+            for n, t in own.items():
+                t.copy_(ema['shadow'][n])
+            engine.num_updates = ema['num_updates']
+        engine._weights_changed()
+        out.update(global_step=int(blob.get('global_step', engine.step_count)), epoch=int(blob.get('epoch', 0)))
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------
+# training state: the native one-file form, and the DDIM code base's `ckpt.pth` list
+# --------------------------------------------------------------------------------------------------------
+TRAINING_STATE_VERSION = 1
+
+
+def _engine_modules(engine):
+    """[(key in the file, module)] whose weights a training-state file holds."""
+    mods = [('weights', engine.model)]
+    if getattr(engine, 'embedder', None) is not None:
+        mods.append(('embedder', engine.embedder))
+    return mods
+
+
+def _is_writer(engine):
+    import torch.distributed as dist
+    from .sweep import dist_active
+    active = dist_active(engine.group)
+    return active, (not active or dist.get_rank(engine.group) == 0)
+
+
+def save_training_state(path, engine):
+    """One file to stop a finetune and go on later, bit for bit: the weights by parameter name (for the LDM engine the embedder's
+    too) and engine.state_dict() (train_state.py: moments, EMA shadow, counters, LR schedule, layout, hyper-parameters).  Plain
+    tensors, numbers, strings and lists: it loads under weights_only=True.  The model is NOT described: rebuild it first as today
+    (load_pruned, the whole-module pickle, or the config).  The teacher of a distillation engine, the data-loader position and
+    host generators stay with the caller.  Under a process group the state is the same on every rank: rank 0 writes, every
+    rank returns once the file is there.  Raises ValueError in the middle of an accumulation window."""
+    active, writer = _is_writer(engine)
+    state = engine.state_dict(device='cpu') if writer else engine.state_dict()      # (every rank checks the window)
+    if writer:
+        blob = dict(format_version=TRAINING_STATE_VERSION, engine=type(engine).__name__, training_state=state)
+        for key, mod in _engine_modules(engine):
+            blob[key] = {k: v.detach().cpu().clone() for k, v in mod.state_dict().items()}
+        tmp = os.fspath(path) + '.tmp'
+        torch.save(blob, tmp)
+        os.replace(tmp, os.fspath(path))
+    if active:
+        import torch.distributed as dist
+        dist.barrier(group=engine.group)
+
+
+def load_training_state(path, engine, strict=True):
+    """Load a save_training_state file into `engine` and its (already rebuilt) model in place: weights into the parameters (views
+    of the engine's flat buffer), the state through engine.load_state_dict(strict=strict).  Every rank loads.  A file taken at
+    another parameter layout (an un-pruned state for a pruned model), or whose state fails any other check of
+    engine.check_state_dict, raises ValueError before anything is written."""
+    from . import train_state
+    blob = torch.load(os.fspath(path), map_location='cpu', weights_only=True)
+    if blob.get('format_version') != TRAINING_STATE_VERSION:
+        raise ValueError('unsupported training-state file format %r' % (blob.get('format_version'),))
+    if blob.get('engine') != type(engine).__name__:
+        raise ValueError('the file holds a %s state, the engine is a %s' % (blob.get('engine'), type(engine).__name__))
+    state = blob['training_state']
+    train_state.check_layout(train_state.param_layout(engine._state_named()), state['layout'])
+    todo = []
+    for key, mod in _engine_modules(engine):
+        own, got = mod.state_dict(), blob[key]
+        if list(own) != list(got):
+            raise ValueError('%s: the file\'s tensor names differ from the model\'s (%s)' % (key, sorted(set(own) ^ set(got))[:5]))
+        for k, t in own.items():
+            if tuple(t.shape) != tuple(got[k].shape):
+                raise ValueError('%s.%s: file shape %s, model shape %s' % (key, k, tuple(got[k].shape), tuple(t.shape)))
+            todo.append((t, got[k]))
+    engine.check_state_dict(state, strict=strict)            # every check before the first write
+    with torch.no_grad():
+        for t, src in todo:
+            t.copy_(src)                                     # state_dict() tensors share the parameters' storage
+    engine.load_state_dict(state, strict=strict)
+    engine._weights_changed()
+
+
+def ddpm_original_parameter_order(keys):
+    """`keys` (parameter names of a ddpm_exp `Model`) in the order of that model's `parameters()`, which is the order its
+    constructor registers modules in (models/diffusion.py:215-299): temb.dense, conv_in, down.<level> (its blocks, then its
+    attentions, then downsample), mid (block_1, attn_1, block_2), up.<level> ascending (blocks, attentions, upsample), norm_out,
+    conv_out; inside a block norm1, conv1, temb_proj, norm2, conv2, nin_shortcut; inside an attention norm, q, k, v, proj_out;
+    weight before bias.  Adam's state indices and EMAHelper's shadow LIST are positional in this order -- not UNet2DModel's."""
+    top = {'temb': 0, 'conv_in': 1, 'down': 2, 'mid': 3, 'up': 4, 'norm_out': 5, 'conv_out': 6}
+    res = {a: i for i, (a, _) in enumerate(_RES_O2D)}
+    att = {a: i for i, (a, _) in enumerate(_ATT_O2D)}
+    leaf = {'weight': 0, 'bias': 1}
+
+    def key(k):
+        p = k.split('.')
+        if p[0] not in top or p[-1] not in leaf:
+            raise KeyError('not a ddpm_exp Model parameter: %s' % k)
+        if p[0] == 'temb':
+            mid = (int(p[2]),)
+        elif p[0] in ('down', 'up'):
+            kind = {'block': 0, 'attn': 1, 'downsample': 2, 'upsample': 2}[p[2]]
+            mid = (int(p[1]), kind) + ((int(p[3]), (res if kind == 0 else att)[p[4]]) if kind < 2 else (0, 0))
+        elif p[0] == 'mid':
+            mid = ({'block_1': 0, 'attn_1': 1, 'block_2': 2}[p[1]], (att if p[1] == 'attn_1' else res)[p[2]])
+        else:
+            mid = ()
+        return (top[p[0]],) + mid + (leaf[p[-1]],)
+    return sorted(keys, key=key)
+
+
+def _ddpm_exp_names(engine):
+    """(our parameter names, the same tensors' ddpm_exp names in that model's parameters() order, {ddpm_exp name: ours})."""
+    ours = [n for n, _ in engine.model.named_parameters()]
+    o2d = {o: d for d, o in zip(ours, convert_to_ddpm_original({n: torch.empty(0) for n in ours}))}
+    return ours, ddpm_original_parameter_order(o2d), o2d
+
+
+def save_ddpm_exp_states(path, engine, epoch):
+    """The `ckpt.pth` list of the DDIM code base (runners/diffusion.py:331-344) from a train.FinetuneEngine:
+    [state dict in that code base's key names, optimizer.state_dict(), epoch, step, EMAHelper's shadow list (with EMA)] --
+    what its `--resume_training` reads (:236-248; element 0 as a state dict is its `else` branch).  Adam's indices and the shadow
+    list are positional in the order of THAT model's parameters() (ddpm_original_parameter_order); the attention projections
+    are 1x1 convolutions there, so their weights, moments and shadow are written as [C, C, 1, 1].  Under a process group rank 0
+    writes and every rank returns once the file is there, as save_training_state."""
+    engine._check_window('save_ddpm_exp_states()')
+    ours, order, o2d = _ddpm_exp_names(engine)
+    named = dict(engine.model.named_parameters())
+    opt = engine.optimizer_state_dict()
+
+    def to_orig(by_ours):
+        conv = convert_to_ddpm_original(by_ours)
+        return [conv[o] for o in order]
+    weights = to_orig({n: named[n].detach().cpu().clone() for n in ours})
+    m = to_orig({n: opt['state'][i]['exp_avg'] for i, n in enumerate(ours)})
+    v = to_orig({n: opt['state'][i]['exp_avg_sq'] for i, n in enumerate(ours)})
+    state = {i: dict(step=opt['state'][0]['step'].clone(), exp_avg=m[i], exp_avg_sq=v[i]) for i in range(len(order))}
+    states = [dict(zip(order, weights)), dict(state=state, param_groups=opt['param_groups']), int(epoch), int(engine.step_count)]
+    if engine.ema is not None:
+        states.append(to_orig({n: t.detach().cpu().clone() for n, t in engine.ema_state().items()}))
+    active, writer = _is_writer(engine)
+    if writer:
+        tmp = os.fspath(path) + '.tmp'
+        torch.save(states, tmp)
+        os.replace(tmp, os.fspath(path))
+    if active:
+        import torch.distributed as dist
+        dist.barrier(group=engine.group)
+
+
+def load_ddpm_exp_states(path, engine):
+    """Read a `ckpt.pth` list (a path or the list itself) into a train.FinetuneEngine and its model in place; returns (epoch, step).
+    The hyper-parameters come from the ENGINE, not from the file's param_groups (the reference overrides eps the same way,
+    runners/diffusion.py:243).  A list whose element 0 is a pickled module (what the reference's own loop writes) is refused: save
+    that module's state_dict() instead, or rebuild the model from it first."""
+    import pickle
+    if isinstance(path, (str, os.PathLike)):
+        try:
+            states = torch.load(os.fspath(path), map_location='cpu', weights_only=True)
+        except pickle.UnpicklingError as e:
+            raise ValueError('%s does not load as plain tensors: element 0 of a ckpt.pth written by the reference\'s training loop is '
+                             'a pickled module; store its state_dict() there instead (%s)' % (path, str(e).splitlines()[0])) from None
+    else:
+        states = path
+    if not isinstance(states, (list, tuple)) or len(states) < 4:
+        raise ValueError('a ckpt.pth holds [state dict, optimizer state, epoch, step(, ema list)]')
+    if isinstance(states[0], torch.nn.Module) or not isinstance(states[0], dict):
+        raise ValueError('element 0 of the ckpt.pth list is a %s, not a state dict: a pickled module is not read here'
+                         % type(states[0]).__name__)
+    engine._check_window('load_ddpm_exp_states()')
+    ours, order, o2d = _ddpm_exp_names(engine)
+    named = dict(engine.model.named_parameters())
+    if sorted(states[0]) != sorted(order):
+        raise ValueError('the checkpoint\'s parameter names differ from the model\'s (%s)' % sorted(set(states[0]) ^ set(order))[:5])
+    w = convert_ddpm_original(dict(states[0]))
+    for n in ours:
+        if tuple(w[n].shape) != tuple(named[n].shape):
+            raise ValueError('%s: checkpoint shape %s, model shape %s' % (n, tuple(w[n].shape), tuple(named[n].shape)))
+    opt = states[1]
+    ids = [i for g in opt['param_groups'] for i in g['params']]
+    if len(ids) != len(order):
+        raise ValueError('the optimizer state covers %d parameters, the model has %d' % (len(ids), len(order)))
+    pos = {n: i for i, n in enumerate(ours)}
+
+    def to_ours(tensors):                                    # positional in `order` -> indexed by our parameter order
+        conv = convert_ddpm_original(dict(zip(order, tensors)))
+        return [conv[n] for n in ours]
+    state = {}
+    if opt['state']:
+        m = to_ours([opt['state'][i]['exp_avg'] for i in ids])
+        v = to_ours([opt['state'][i]['exp_avg_sq'] for i in ids])
+        state = {pos[n]: dict(step=opt['state'][ids[0]]['step'], exp_avg=m[pos[n]], exp_avg_sq=v[pos[n]]) for n in ours}
+        steps = {float(opt['state'][i]['step']) for i in ids}
+        if len(steps) != 1:
+            raise ValueError('the parameters are at different optimizer steps: %s' % sorted(steps))
+    shadow = None
+    if engine.ema is not None:
+        if len(states) < 5:
+            raise ValueError('the engine keeps an EMA shadow, the ckpt.pth list has none (element 4)')
+        shadow = to_ours(list(states[4]) if isinstance(states[4], (list, tuple)) else list(states[4].values()))
+        for n, t in zip(ours, shadow):
+            if tuple(t.shape) != tuple(named[n].shape):
+                raise ValueError('EMA shadow of %s: shape %s, model shape %s' % (n, tuple(t.shape), tuple(named[n].shape)))
+    engine.load_optimizer_state_dict(dict(state=state, param_groups=[dict(params=list(range(len(ours))))]))
+    with torch.no_grad():
+        for n in ours:
+            named[n].data.copy_(w[n])
+        if shadow is not None:
+            for (n, dst), t in zip(engine.ema_state().items(), shadow):
+                dst.copy_(t)
+    engine._weights_changed()
+    return int(states[2]), int(states[3])

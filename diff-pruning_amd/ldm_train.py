@@ -12,8 +12,10 @@ p_losses :1022-1056) + `torch.optim.AdamW(params, lr=lr)` over `list(unet.parame
 
 Parameters, gradients and moments live in flat fp32 buffers (UNet first, embedder last), so the update is ONE launch of
 dp_adamw_ema (two with the EMA: the shadow covers the UNet only, LitEma(self.model)) and the data-parallel exchange a handful of
-all-reduces over contiguous ranges.  No LR scheduler (use_scheduler is off in the config), no learn_logvar, no gradient
-accumulation, no native replay of the step.
+all-reduces over contiguous ranges.  Gradient accumulation (accumulate_grad_batches, main.py:707-722): a window of k calls is one
+optimizer step; LitEma runs at the end of EVERY batch (ddpm.py:366-368), so the k-1 calls that do not step update the shadow alone
+(dp_ema_update).  The training state (train_state.TrainState) makes a run resumable bit for bit.  No LR scheduler (use_scheduler
+is off in the config), no learn_logvar, no native replay of the step.
 """
 import contextlib
 
@@ -23,6 +25,7 @@ import torch
 from . import ops
 from .ldm_sweep import LdmSchedule, encode_first_stage
 from .sweep import StepThrottle, dist_active
+from .train_state import TrainState
 
 
 def learning_rate(base_lr, batch_size, n_gpus, accumulate_grad_batches=1):
@@ -43,15 +46,25 @@ def _require_hip_device(dev):
         raise RuntimeError('the LDM finetune step runs on the MI355X HIP kernels only')
 
 
-class LdmFinetuneEngine:
+class LdmFinetuneEngine(TrainState):
+    TORCH_OPTIMIZER = 'AdamW'
+
     def __init__(self, model, embedder, schedule=None, lr=1.28e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 use_ema=False, ema_decay=0.9999, group=None, first_stage=None, scale_factor=1.0):
+                 use_ema=False, ema_decay=0.9999, group=None, first_stage=None, scale_factor=1.0,
+                 accumulate_grad_batches=1):
         """model: an ldm.UNetModel (pruned or not); embedder: an ldm_sweep.ClassEmbedder, trained with it.
         lr: see learning_rate().  use_ema: keep LitEma's shadow of the UNet (cin256-v2 has use_ema False).
         group: torch.distributed process group of the data-parallel step (None = the default group when initialised): every rank
         steps on its shard of the batch, the gradients (UNet and embedder) are summed over ranks before the update, and the loss
         and gradient of a rank are its share of the mean over the GLOBAL batch.
-        first_stage / scale_factor: the VQModel and latent scale step_images() encodes with."""
+        first_stage / scale_factor: the VQModel and latent scale step_images() encodes with.
+        accumulate_grad_batches = k: a window of k step() calls is one optimizer step on k * B latents per rank (see step()).
+        state_dict() / load_state_dict() (train_state.TrainState) carry the training state; the data-loader position and host
+        generators are not part of it and stay with the caller."""
+        k = int(accumulate_grad_batches)
+        if k < 1 or k != accumulate_grad_batches:
+            raise ValueError('accumulate_grad_batches must be a positive integer, got %r' % (accumulate_grad_batches,))
+        self.accum, self._micro = k, 0
         from .ldm import UNetModel
         from .ldm_sweep import ClassEmbedder
         if not isinstance(model, UNetModel):
@@ -103,6 +116,22 @@ class LdmFinetuneEngine:
         self._stash = None
         self._throttle = StepThrottle()
 
+    # ---- train_state.TrainState
+    def _state_named(self):
+        from .checkpoint import LDM_UNET_PREFIX, LDM_EMBEDDER_PREFIX
+        return ([(LDM_UNET_PREFIX + n, p) for n, p in self.model.named_parameters()] +
+                [(LDM_EMBEDDER_PREFIX + n, p) for n, p in self.embedder.named_parameters()])
+
+    def _state_hyper(self):
+        return dict(lr=self.lr, betas=list(self.betas), eps=self.eps, weight_decay=self.weight_decay, ema_decay=self.ema_decay,
+                    max_grad_norm=None, dropout_seed=None, accumulation=int(self.accum), kd_weights=None, use_ema=self.ema is not None)
+
+    def _state_counters(self):
+        return dict(step_count=int(self.step_count), num_updates=int(self.num_updates))
+
+    def _load_counters(self, sd):
+        self.step_count, self.num_updates = int(sd['step_count']), int(sd['num_updates'])
+
     # ---- LitEma (ema.py) -----------------------------------------------------------------------------------------
     def ema_state(self):
         """The shadow as a {UNet parameter name: tensor} dict (views of the flat shadow buffer)."""
@@ -144,7 +173,11 @@ class LdmFinetuneEngine:
     def step(self, x_start, class_ids, noise=None, timesteps=None, generator=None, global_batch=None):
         """One optimizer step on latents x_start [B, C, H, W] with class ids [B].  timesteps default to randint(0, T, (B,)) per
         image (ddpm.py:871), noise to randn_like (both from `generator`, a CPU generator, when given).  Returns nothing that forces a
-        host synchronisation: `last_loss` is a [1] device tensor (this rank's share of the global mean under a process group)."""
+        host synchronisation: `last_loss` is a [1] device tensor (this rank's share of the global mean under a process group).
+        With accumulate_grad_batches = k a window is k calls: call 0 zeroes the gradient, every call adds its share of the mean over
+        the B * world * k latents of the window, calls 0 .. k-2 leave parameters and moments alone (no collective, packed operands
+        kept) and update the LitEma shadow only -- num_updates and the warm-up decay advance per BATCH -- and call k-1 reduces and
+        runs the fused update."""
         import torch.distributed as dist
         use_dist = dist_active(self.group)
         model, emb_w = self.model, self.embedder.embedding.weight
@@ -153,7 +186,8 @@ class LdmFinetuneEngine:
         ids = ops.check_class_ids(class_ids, emb_w.shape[0])             # host-side: a ValueError, never a device fault
         if ids.numel() != B:
             raise ValueError('%d class ids for %d latents' % (ids.numel(), B))
-        gb = global_batch if global_batch is not None else (B * dist.get_world_size(self.group) if use_dist else B)
+        k, j = self.accum, self._micro
+        gb = global_batch if global_batch is not None else (B * dist.get_world_size(self.group) if use_dist else B) * k
         T = self.schedule.num_timesteps
         if timesteps is None:
             timesteps = torch.randint(0, T, (B,), generator=generator)
@@ -165,14 +199,16 @@ class LdmFinetuneEngine:
         t = timesteps.to(device=dev, dtype=torch.long).contiguous()
         ids = ids.to(dev).contiguous()
         model.train()
-        eng = model.engine()
+        # inside a window the weights did not change: the engine of call 0 and its packed operands are kept (model.engine() drops them)
+        eng = model.engine() if j == 0 or getattr(model, '_engine', None) is None else model._engine
         eng.bind({n: p.detach() for n, p in model.named_parameters()}, {n: p.grad for n, p in model.named_parameters()})
-        if hasattr(ops, 'pack_weight_batch'):
+        if hasattr(ops, 'pack_weight_batch') and j == 0:
             eng.prepare_packs()              # the last update invalidated every packed operand: re-pack in a few launches
         c = emb_w.detach().index_select(0, ids)[:, None, :]              # ClassEmbedder.forward, differentiated below
         sa, sb = self.schedule.tables(dev)
         x_noisy = ops.q_sample(x_start, noise, sa, sb, t)
-        self.flat_g.zero_()                                              # optimizer.zero_grad()
+        if j == 0:
+            self.flat_g.zero_()                                          # optimizer.zero_grad()
         out = eng.forward(x_noisy, t, c, save=True)
         n_glob = gb * (out.numel() // B)                                 # mean_B(mean_CHW) == mean over every element
         loss, dout = ops.mse_fwd_bwd(out, noise, 2.0 / n_glob, 1.0 / n_glob)
@@ -180,6 +216,15 @@ class LdmFinetuneEngine:
         if dctx.shape[1] != 1:
             raise NotImplementedError('the class embedder yields one context token per image')
         ops.embedding_bwd(ids, dctx.reshape(B, dctx.shape[2]).contiguous(), emb_w.grad)
+        if j < k - 1:                                                    # the gradient stays in flat_g: LitEma alone (on_train_batch_end)
+            if self.ema is not None:
+                self.num_updates += 1
+                ops.ema_update(self.ema, self.flat_p[:self.n_unet], lit_ema_decay(self.ema_decay, self.num_updates))
+            self._micro = j + 1
+            self.last_loss = loss
+            self._throttle.mark()
+            return loss
+        self._micro = 0
         if use_dist:
             self._reduce_grads(dist)
         self.step_count += 1

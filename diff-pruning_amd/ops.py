@@ -1624,6 +1624,19 @@ def adamw_ema(p_, g, m, v, ema, lr, b1, b2, eps, weight_decay, step, ema_decay=0
                                 s['one_minus_b2'], s['sqrt_bc2'], eps, s['step_size'], float(ema_decay), _stream()), 'dp_adamw_ema')
 
 
+def ema_update(shadow, p_, decay):
+    """LitEma's update alone: `shadow -= (1 - decay) * (shadow - p)` over flat fp32 buffers, 1 - decay formed in fp32 as LitEma
+    (and dp_adamw_ema) form it: the same bits as the EMA half of adamw_ema(..., ema_decay=decay).  decay: the decay in force at
+    this update (ldm_train.lit_ema_decay)."""
+    n = p_.numel()
+    for t in (shadow, p_):
+        assert t.is_cuda and t.dtype == _f32 and t.is_contiguous() and t.numel() == n, 'ema_update: flat contiguous fp32 device buffers'
+    import numpy as np
+    omd = float(np.float32(1) - np.float32(decay))
+    L.check(_lib().dp_ema_update(_p(shadow), _p(p_), n, omd, _stream()), 'dp_ema_update')
+    return shadow
+
+
 EMBEDDING_BWD_MAX_ROWS = 4096
 
 

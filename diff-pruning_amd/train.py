@@ -22,6 +22,7 @@ import torch
 
 from . import ops
 from .sweep import StepThrottle, dist_active
+from .train_state import TrainState
 
 
 def antithetic_timesteps(bsz, num_train_timesteps, generator=None):
@@ -196,10 +197,10 @@ def load_teacher(src, device, ch=None, ch_mult=None, num_res_blocks=None, attn_r
     return model
 
 
-class FinetuneEngine:
+class FinetuneEngine(TrainState):
     def __init__(self, model, scheduler, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, ema_decay=0.9999, max_grad_norm=1.0,
                  use_ema=True, group=None, dropout=None, lr_scheduler=None, dropout_seed=0, replay=None, teacher=None,
-                 kd_weights=(0.7, 0.3)):
+                 kd_weights=(0.7, 0.3), gradient_accumulation_steps=1):
         """dropout: None keeps whatever `set_dropout(model, p)` has set on the nn.Dropout holders; a float sets it.
         lr_scheduler: a `LambdaLR` from `get_scheduler` (its base_lr is the learning rate) or None (constant `lr`).
         replay: True / False / None (automatic: single-process steps on a cuda device, DP_FINETUNE_REPLAY=0 disables) -- the step is
@@ -211,7 +212,17 @@ class FinetuneEngine:
         teacher: None (the eps loss), or a frozen UNet2DModel on the model's device whose no-grad forward of the same noisy input
         enters the distillation loss with weights kd_weights = (w_kd, w_eps) (functions/losses.py:17-31).  It runs in eval mode
         without dropout; its packed operands are built once and kept (it is never written); EMA and the optimizer see the student
-        only.  `last_loss_terms` holds the [kd, eps] device tensor of the last step."""
+        only.  `last_loss_terms` holds the [kd, eps] device tensor of the last step.
+        gradient_accumulation_steps = k: a window of k step() calls is ONE optimizer step on a batch of k * B images per rank,
+        sharded in time (see step()).  With k > 1 the step runs eagerly (replay=None resolves to eager, replay=True raises).
+        state_dict() / load_state_dict() (train_state.TrainState) carry the training state; the teacher, the data-loader position
+        and host generators are not part of it and stay with the caller."""
+        k = int(gradient_accumulation_steps)
+        if k < 1 or k != gradient_accumulation_steps:
+            raise ValueError('gradient_accumulation_steps must be a positive integer, got %r' % (gradient_accumulation_steps,))
+        if k > 1 and replay:
+            raise ValueError('replay=True with gradient_accumulation_steps = %d: an accumulating step runs eagerly' % k)
+        self.accum, self._micro = k, 0
         if teacher is not None:
             kd_weights = _check_kd_weights(kd_weights)
             _check_teacher(teacher, model, next(model.parameters()).device)
@@ -267,6 +278,16 @@ class FinetuneEngine:
             self._teacher_pin.__enter__()
             self._teacher_eng = self._teacher_pin.eng
             self.teacher, self.kd_weights = teacher, kd_weights
+
+    # ---- train_state.TrainState
+    def _state_named(self):
+        return list(self.model.named_parameters())
+
+    def _state_hyper(self):
+        return dict(lr=float(self.lr), betas=[float(b) for b in self.betas], eps=float(self.eps), weight_decay=0.0,
+                    ema_decay=float(self.ema_decay), max_grad_norm=float(self.max_grad_norm), dropout_seed=int(self.dropout_seed),
+                    accumulation=int(self.accum), kd_weights=None if self.kd_weights is None else [float(w) for w in self.kd_weights],
+                    use_ema=self.ema is not None)
 
     def ema_state(self):
         """EMA parameters as a {name: tensor} dict (views of the flat EMA buffer)."""
@@ -338,7 +359,7 @@ class FinetuneEngine:
 
     def _replay_wanted(self, use_dist, dev):
         import os
-        if use_dist or dev.type != 'cuda' or getattr(ops, 'IS_MOCK', False) or not hasattr(ops, 'CapturedCall'):
+        if use_dist or dev.type != 'cuda' or getattr(ops, 'IS_MOCK', False) or not hasattr(ops, 'CapturedCall') or self.accum > 1:
             return False                                 # the data-parallel step interleaves collectives with the backward pass
         if self.replay is None:
             return os.environ.get('DP_FINETUNE_REPLAY', '1') != '0'
@@ -449,13 +470,21 @@ class FinetuneEngine:
     def step(self, clean, noise, timesteps, global_batch=None, image_offset=None):
         """Returns the (local share of the) loss as a [1] device tensor; no host synchronisation.
         image_offset: global index of this rank's first image (default rank * B): the dropout masks are functions of the
-        GLOBAL element index, so a sharded step draws the masks of the un-sharded one."""
+        GLOBAL element index, so a sharded step draws the masks of the un-sharded one.
+        With gradient_accumulation_steps = k a window is k calls: one batch of k * B images per rank sharded in time.  Call 0
+        zeroes the gradient; every call runs forward, loss and backward at the global batch B * world * k and the dropout-mask step
+        step_count + 1 (default image_offset (rank * k + j) * B: the masks of the un-split batch) and accumulates; calls 0 .. k-2
+        touch neither parameters, moments, step_count nor the LR schedule, issue no collective and keep the packed operands; call
+        k-1 all-reduces, clips the ACCUMULATED gradient, updates and steps the LR schedule once.  Every call returns its share of
+        the global mean."""
         import torch.distributed as dist
         use_dist = dist_active(self.group)
         B = clean.shape[0]
-        gb = global_batch if global_batch is not None else (B * dist.get_world_size(self.group) if use_dist else B)
+        k, j = self.accum, self._micro
+        last = j == k - 1
+        gb = global_batch if global_batch is not None else (B * dist.get_world_size(self.group) if use_dist else B) * k
         if image_offset is None:
-            image_offset = dist.get_rank(self.group) * B if use_dist else 0
+            image_offset = ((dist.get_rank(self.group) if use_dist else 0) * k + j) * B
         model = self.model
         model.train()                                     # ddpm_train.py:430
         dev = self.flat_p.device
@@ -468,10 +497,11 @@ class FinetuneEngine:
                                        timesteps.to(device=dev, dtype=torch.long).contiguous(), gb, image_offset)
         clean = clean.to(dev, torch.float32).contiguous()
         noise = noise.to(dev, torch.float32).contiguous()
-        eng = model.engine()
+        # inside a window the weights did not change: the engine of call 0 and its packed operands are kept (model.engine() drops them)
+        eng = model.engine() if j == 0 or getattr(model, '_engine', None) is None else model._engine
         eng.bind({n: p.detach() for n, p in model.named_parameters()}, {n: p.grad for n, p in model.named_parameters()})
         eng.set_dropout(getattr(model, 'dropout_table', dict)(), self.dropout_seed, self.step_count + 1, image_offset)
-        if hasattr(ops, 'pack_weight_batch'):
+        if hasattr(ops, 'pack_weight_batch') and j == 0:
             eng.prepare_packs()          # the last optimizer step invalidated every packed operand: re-pack in a few launches
         # the batched time-embedding backward finalises the time_emb_proj gradients only at the END of the backward pass: it is
         # switched off when gradient buckets are all-reduced at the segment milestones
@@ -480,7 +510,8 @@ class FinetuneEngine:
         noisy = ops.add_noise(clean, noise, self.acp, t)
         if self.teacher is not None:
             t_out, side = self._teacher_forward(noisy, t, self._kd_overlap(dev), eng.stream_slot)
-        self.flat_g.zero_()                               # optimizer.zero_grad()
+        if j == 0:
+            self.flat_g.zero_()                           # optimizer.zero_grad()
         out = eng.forward(noisy, t, save=True)
         if self.teacher is None:
             loss, dout = ops.mse_fwd_bwd(out, noise, 2.0 / gb, 1.0 / gb)
@@ -490,6 +521,11 @@ class FinetuneEngine:
             loss, self.last_loss_terms = terms[0:1], terms[1:3]
             del t_out
         pending = []
+        if not last:                                      # the gradient stays in flat_g: no collective, no update, no LR step
+            eng.backward(dout)
+            self._micro = j + 1
+            self._throttle.mark()
+            return loss
         if use_dist:
             # bucketed all-reduce overlapped with the backward pass: each bucket's collective (RCCL over xGMI) is enqueued as
             # soon as its gradients are final and runs while the remaining layers' MFMA kernels execute
@@ -509,6 +545,7 @@ class FinetuneEngine:
         nc = ops.clip_coef(partial, self.max_grad_norm)
         self.last_grad_norm = nc[0:1]
         self.step_count += 1
+        self._micro = 0
         lr = self.lr_scheduler.get_last_lr()[0] if self.lr_scheduler is not None else self.lr
         self.last_lr = lr
         ops.adam_ema(self.flat_p, self.flat_g, self.m, self.v, self.ema, nc[1:2], lr, self.betas[0], self.betas[1],

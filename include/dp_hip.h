@@ -386,6 +386,11 @@ int dp_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long l
 int dp_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* clip_coef,
                  float p_scale, float one_minus_b1, float b2, float one_minus_b2, float sqrt_bc2, float eps,
                  float step_size, float ema_decay, void* stream);
+/* LitEma's update alone (ldm/modules/ema.py:40-44): s[i] -= one_minus_decay * (s[i] - p[i]), i < n, rounded after every operation --
+ * the EMA half of dp_adamw_ema bit for bit (one_minus_decay = the fp32 difference 1 - decay).  For the batches of a gradient-
+ * accumulation window that end without an optimizer step.  16-byte accesses when both pointers are 16-byte aligned, 4-byte
+ * accesses for the n % 4 tail and for unaligned views; any n (long long indexing, grid-stride under dp_adamw_ema's cap). */
+int dp_ema_update(float* s, const float* p, long long n, float one_minus_decay, void* stream);
 /* Gradient of an embedding lookup: dW[ids[b], :] += dctx[b, :] for b = 0 .. B-1 (B <= 4096), the rows of a repeated id added in
  * ascending b -- bitwise reproducible, no float atomics.  ids: int64, every id in [0, rows of dW) (checked by the caller). */
 int dp_embedding_bwd(const long long* ids, const float* dctx, int B, int D, float* dW, void* stream);
