@@ -136,6 +136,23 @@ static inline DpDrop dp_drop_host(const dp_dropout* d) {
     return r;
 }
 
+// ---- the flat fp32 update kernels (optim.hip adamw_ema_kernel, ema.hip ema_update_kernel) share what follows
+// LitEma's `shadow.sub_(one_minus_decay * (shadow - param))` (ldm/modules/ema.py:40-44), rounded after every operation: the
+// ONE copy of the expression, so a shadow kept by dp_ema_update and one kept by the fused dp_adamw_ema agree bit for bit.
+__device__ __forceinline__ float dp_lit_ema(float s, float p, float omd) {
+#pragma clang fp contract(off)      // LitEma rounds the difference, the product and the subtraction separately
+    return s - omd * (s - p);
+}
+
+// The host rule of those launchers.  ptr_bits: the OR of every pointer the kernel touches.  The 16-byte path (VEC) iff all of
+// them are 16-byte aligned and n >= 4; the grid is one lane per float4 (per element when !VEC) in blocks of 256, capped at
+// 4096 blocks (16 per CU, grid-stride beyond), at least 1.
+static inline unsigned dp_flat_grid(uintptr_t ptr_bits, long long n, bool* vec) {
+    *vec = (ptr_bits & 15) == 0 && n >= 4;
+    const long long nb = ((*vec ? n / 4 : n) + 255) / 256;
+    return (unsigned)(nb > 4096 ? 4096 : nb < 1 ? 1 : nb);
+}
+
 #define DP_LAUNCH_CHECK() ((int)hipGetLastError())
 // every kernel launch of the library goes through DP_LAUNCH: dp_launch_count() reports launches per step in bench.py, and the
 // stringised kernel expression of each launch is kept in a host-side ring of DP_LAUNCH_RING entries (dp_recent_launches(), so

@@ -38,10 +38,11 @@ extern "C" int dp_clip_coef(const float* partial, int n, float max_norm, float* 
     return DP_LAUNCH_CHECK();
 }
 
-__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, float* __restrict__ ema, long long n,
-                                                       const float* __restrict__ clip_coef, float lr, float b1, float b2,
-                                                       float eps, float bc1, float bc2, float ema_decay) {
+// The Adam + EMA pass both launch variants run: they differ in where {lr, bc1, bc2} come from only.
+__device__ __forceinline__ void adam_ema_pass(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, float* __restrict__ ema, long long n,
+                                              const float* __restrict__ clip_coef, float lr, float b1, float b2, float eps,
+                                              float bc1, float bc2, float ema_decay) {
     const float coef = clip_coef ? clip_coef[0] : 1.0f;
     const float step_size = lr / bc1;
     const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
@@ -56,6 +57,13 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
         p[i] = pi;
         if (ema) ema[i] = (1.0f - ema_decay) * pi + ema_decay * ema[i];
     }
+}
+
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, float* __restrict__ ema, long long n,
+                                                       const float* __restrict__ clip_coef, float lr, float b1, float b2,
+                                                       float eps, float bc1, float bc2, float ema_decay) {
+    adam_ema_pass(p, g, m, v, ema, n, clip_coef, lr, b1, b2, eps, bc1, bc2, ema_decay);
 }
 extern "C" int dp_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* clip_coef,
                            float lr, float b1, float b2, float eps, float bc1, float bc2, float ema_decay, void* stream) {
@@ -83,21 +91,7 @@ __global__ __launch_bounds__(256) void adam_ema_dev_kernel(float* __restrict__ p
                                                            float* __restrict__ v, float* __restrict__ ema, long long n,
                                                            const float* __restrict__ clip_coef, const float* __restrict__ hyper,
                                                            float b1, float b2, float eps, float ema_decay) {
-    const float coef = clip_coef ? clip_coef[0] : 1.0f;
-    const float lr = hyper[0], bc1 = hyper[1], bc2 = hyper[2];
-    const float step_size = lr / bc1;
-    const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float gi = g[i] * coef;
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        const float pi = p[i] - step_size * (mi / denom);
-        p[i] = pi;
-        if (ema) ema[i] = (1.0f - ema_decay) * pi + ema_decay * ema[i];
-    }
+    adam_ema_pass(p, g, m, v, ema, n, clip_coef, hyper[0], b1, b2, eps, hyper[1], hyper[2], ema_decay);
 }
 extern "C" int dp_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* clip_coef,
                                const float* hyper, float b1, float b2, float eps, float ema_decay, void* stream) {
@@ -130,7 +124,7 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
     p = pi;
     m = mi;
     v = vi;
-    if (has_ema) s = s - (1.0f - c.decay) * (s - pi);    // shadow.sub_(one_minus_decay * (shadow - param))
+    if (has_ema) s = dp_lit_ema(s, pi, 1.0f - c.decay);  // shadow.sub_(one_minus_decay * (shadow - param))
 }
 
 template <bool VEC>
@@ -178,15 +172,12 @@ extern "C" int dp_adamw_ema(float* p, const float* g, float* m, float* v, float*
     if (n <= 0) return 0;
     if (!p || !g || !m || !v) return (int)hipErrorInvalidValue;
     const adamw_scalars c = {p_scale, one_minus_b1, b2, one_minus_b2, sqrt_bc2, eps, step_size, ema_decay};
-    const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
-    const bool vec = (bits & 15) == 0 && n >= 4;
-    long long nb = ((vec ? n / 4 : n) + 255) / 256;
-    if (nb > 4096) nb = 4096;                            // 16 blocks of 256 per CU, grid-stride beyond
-    if (nb < 1) nb = 1;
+    bool vec;
+    const unsigned nb = dp_flat_grid((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema, n, &vec);
     if (vec)
-        DP_LAUNCH(adamw_ema_kernel<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, clip_coef, c);
+        DP_LAUNCH(adamw_ema_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, clip_coef, c);
     else
-        DP_LAUNCH(adamw_ema_kernel<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, clip_coef, c);
+        DP_LAUNCH(adamw_ema_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, clip_coef, c);
     return DP_LAUNCH_CHECK();
 }
 

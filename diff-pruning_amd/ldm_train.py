@@ -10,7 +10,8 @@ p_losses :1022-1056) + `torch.optim.AdamW(params, lr=lr)` over `list(unet.parame
     (ops.embedding_bwd: repeated ids added in ascending b, no atomics);  AdamW with decoupled weight decay on EVERY parameter --
     the 1001 embedding rows and the exactly-zero-gradient attn2.to_q / to_k / norm2 included -- and the LitEma shadow of the UNet.
 
-Parameters, gradients and moments live in flat fp32 buffers (UNet first, embedder last), so the update is ONE launch of
+Parameters, gradients and moments live in flat fp32 buffers (UNet first, embedder last; train_state.TrainState, the core shared
+with train.FinetuneEngine: flat state, accumulation window, exchange ranges, EMA swap), so the update is ONE launch of
 dp_adamw_ema (two with the EMA: the shadow covers the UNet only, LitEma(self.model)) and the data-parallel exchange a handful of
 all-reduces over contiguous ranges.  Gradient accumulation (accumulate_grad_batches, main.py:707-722): a window of k calls is one
 optimizer step; LitEma runs at the end of EVERY batch (ddpm.py:366-368), so the k-1 calls that do not step update the shadow alone
@@ -24,8 +25,12 @@ import torch
 
 from . import ops
 from .ldm_sweep import LdmSchedule, encode_first_stage
-from .sweep import StepThrottle, dist_active
-from .train_state import TrainState
+from .sweep import dist_active
+from .train_state import TrainState, flat_views, segment_ranges
+
+# the exchange order of the data-parallel step = the order the backward pass finishes the segments: output path + head, middle,
+# input path, time embedding, embedder
+_SEGMENT_ORDER = {'output_blocks': 0, 'middle_block': 1, 'input_blocks': 2, 'time_embed': 3, 'cond_stage_model': 4}
 
 
 def learning_rate(base_lr, batch_size, n_gpus, accumulate_grad_batches=1):
@@ -59,12 +64,9 @@ class LdmFinetuneEngine(TrainState):
         and gradient of a rank are its share of the mean over the GLOBAL batch.
         first_stage / scale_factor: the VQModel and latent scale step_images() encodes with.
         accumulate_grad_batches = k: a window of k step() calls is one optimizer step on k * B latents per rank (see step()).
-        state_dict() / load_state_dict() (train_state.TrainState) carry the training state; the data-loader position and host
-        generators are not part of it and stay with the caller."""
-        k = int(accumulate_grad_batches)
-        if k < 1 or k != accumulate_grad_batches:
-            raise ValueError('accumulate_grad_batches must be a positive integer, got %r' % (accumulate_grad_batches,))
-        self.accum, self._micro = k, 0
+        The flat buffers, the window and state_dict() / load_state_dict() come from train_state.TrainState; the data-loader
+        position and host generators are not part of the training state and stay with the caller."""
+        self._init_window(accumulate_grad_batches, 'accumulate_grad_batches')
         from .ldm import UNetModel
         from .ldm_sweep import ClassEmbedder
         if not isinstance(model, UNetModel):
@@ -76,45 +78,16 @@ class LdmFinetuneEngine(TrainState):
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
         self.ema_decay, self.group = float(ema_decay), group
         self.first_stage, self.scale_factor = first_stage, scale_factor
-        unet_params = list(model.parameters())
-        params = unet_params + list(embedder.parameters())               # ddpm.py:1374-1377
+        params = list(model.parameters()) + list(embedder.parameters())  # ddpm.py:1374-1377
         dev = params[0].device
         _require_hip_device(dev)
         if any(p.device != dev for p in params):
             raise ValueError('the UNet and the embedder must be on the same device')
-        total = sum(p.numel() for p in params)
-        self.n_unet = sum(p.numel() for p in unet_params)
-        self.flat_p = torch.empty(total, dtype=torch.float32, device=dev)
-        self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        off = 0
-        for p in params:                     # re-home parameters into the flat buffer (views keep nn.Module semantics)
-            n = p.numel()
-            self.flat_p[off:off + n].copy_(p.data.reshape(-1))
-            p.data = self.flat_p[off:off + n].view_as(p)
-            p.grad = self.flat_g[off:off + n].view_as(p)
-            off += n
-        # exchange ranges of the data-parallel step, in the order the backward pass finishes them: output path + head, middle,
-        # input path, time embedding, embedder
-        self._buckets, off = [], 0
-        names = [n for n, _ in model.named_parameters()] + ['cond_stage_model.' + n for n, _ in embedder.named_parameters()]
-        for name, p in zip(names, params):
-            seg = name.split('.')[0]
-            seg = {'out': 'output_blocks'}.get(seg, seg)
-            if self._buckets and self._buckets[-1][0] == seg:
-                self._buckets[-1][2] = off + p.numel()
-            else:
-                self._buckets.append([seg, off, off + p.numel()])
-            off += p.numel()
-        order = {'output_blocks': 0, 'middle_block': 1, 'input_blocks': 2, 'time_embed': 3, 'cond_stage_model': 4}
-        self._buckets.sort(key=lambda b: (order.get(b[0], 5), b[1]))
-        self.m = torch.zeros_like(self.flat_p)
-        self.v = torch.zeros_like(self.flat_p)
-        self.ema = self.flat_p[:self.n_unet].clone() if use_ema else None
+        self.n_unet = sum(p.numel() for p in model.parameters())
+        self._init_flat(use_ema, self.n_unet)                            # LitEma(self.model): the shadow covers the UNet only
+        self._buckets = sorted(segment_ranges(self._state_named(), self._segment), key=lambda b: (_SEGMENT_ORDER.get(b[0], 5), b[1]))
         self.num_updates = 0                 # LitEma.num_updates
-        self.step_count = 0
         self.last_loss = None
-        self._stash = None
-        self._throttle = StepThrottle()
 
     # ---- train_state.TrainState
     def _state_named(self):
@@ -132,37 +105,32 @@ class LdmFinetuneEngine(TrainState):
     def _load_counters(self, sd):
         self.step_count, self.num_updates = int(sd['step_count']), int(sd['num_updates'])
 
+    @staticmethod
+    def _segment(name):
+        from .checkpoint import LDM_UNET_PREFIX
+        seg = (name[len(LDM_UNET_PREFIX):] if name.startswith(LDM_UNET_PREFIX) else name).split('.')[0]
+        return {'out': 'output_blocks'}.get(seg, seg)
+
     # ---- LitEma (ema.py) -----------------------------------------------------------------------------------------
     def ema_state(self):
         """The shadow as a {UNet parameter name: tensor} dict (views of the flat shadow buffer)."""
         if self.ema is None:
             raise RuntimeError('LdmFinetuneEngine was built with use_ema=False')
-        out, off = {}, 0
-        for n, p in self.model.named_parameters():
-            out[n] = self.ema[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        return out
-
-    def _weights_changed(self):
-        eng = getattr(self.model, '_engine', None)
-        if eng is not None:
-            eng.packs.clear()
+        return flat_views(self.ema, self.model.named_parameters())
 
     @contextlib.contextmanager
     def ema_scope(self):
-        """ddpm.py:172-186: store the live UNet weights, copy the shadow in, restore on exit.  Without EMA: a no-op scope."""
+        """ddpm.py:172-186: store the live UNet weights, copy the shadow in, restore on exit (TrainState._live_*).  Without EMA: a
+        no-op scope."""
         if self.ema is None:
             yield
             return
-        self._stash = self.flat_p[:self.n_unet].clone()                  # LitEma.store
-        self.flat_p[:self.n_unet].copy_(self.ema)                        # LitEma.copy_to
-        self._weights_changed()
+        self._live_store()                                               # LitEma.store
+        self._live_from_shadow()                                         # LitEma.copy_to
         try:
             yield
         finally:
-            self.flat_p[:self.n_unet].copy_(self._stash)                 # LitEma.restore
-            self._stash = None
-            self._weights_changed()
+            self._live_restore()                                         # LitEma.restore
 
     # ---- the step ------------------------------------------------------------------------------------------------
     def _reduce_grads(self, dist):
@@ -199,11 +167,7 @@ class LdmFinetuneEngine(TrainState):
         t = timesteps.to(device=dev, dtype=torch.long).contiguous()
         ids = ids.to(dev).contiguous()
         model.train()
-        # inside a window the weights did not change: the engine of call 0 and its packed operands are kept (model.engine() drops them)
-        eng = model.engine() if j == 0 or getattr(model, '_engine', None) is None else model._engine
-        eng.bind({n: p.detach() for n, p in model.named_parameters()}, {n: p.grad for n, p in model.named_parameters()})
-        if hasattr(ops, 'pack_weight_batch') and j == 0:
-            eng.prepare_packs()              # the last update invalidated every packed operand: re-pack in a few launches
+        eng = self._window_engine(ops)
         c = emb_w.detach().index_select(0, ids)[:, None, :]              # ClassEmbedder.forward, differentiated below
         sa, sb = self.schedule.tables(dev)
         x_noisy = ops.q_sample(x_start, noise, sa, sb, t)
@@ -220,11 +184,9 @@ class LdmFinetuneEngine(TrainState):
             if self.ema is not None:
                 self.num_updates += 1
                 ops.ema_update(self.ema, self.flat_p[:self.n_unet], lit_ema_decay(self.ema_decay, self.num_updates))
-            self._micro = j + 1
             self.last_loss = loss
-            self._throttle.mark()
+            self._end_call(last=False)
             return loss
-        self._micro = 0
         if use_dist:
             self._reduce_grads(dist)
         self.step_count += 1
@@ -241,7 +203,7 @@ class LdmFinetuneEngine(TrainState):
                           self.weight_decay, self.step_count)
         eng.packs.clear()                                                # weights changed: packed operands are stale
         self.last_loss = loss
-        self._throttle.mark()
+        self._end_call(last=True)
         return loss
 
     def step_images(self, images, class_ids, **kw):

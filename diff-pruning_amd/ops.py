@@ -1584,9 +1584,13 @@ def clip_coef(partial, max_norm):
     return out       # [norm, coef]
 
 
+def bias_corrections(b1, b2, step):
+    """Adam's (1 - b1^step, 1 - b2^step) in Python doubles; every launcher below rounds them to fp32 once, by the call."""
+    return 1.0 - b1 ** step, 1.0 - b2 ** step
+
+
 def adam_ema(p_, g, m, v, ema, coef, lr, b1, b2, eps, step, ema_decay):
-    bc1 = 1.0 - b1 ** step
-    bc2 = 1.0 - b2 ** step
+    bc1, bc2 = bias_corrections(b1, b2, step)
     L.check(_lib().dp_adam_ema(_p(p_), _p(g), _p(m), _p(v), _p(ema), p_.numel(), _p(coef), lr, b1, b2, eps, bc1, bc2,
                                ema_decay, _stream()), 'dp_adam_ema')
 
@@ -1595,7 +1599,7 @@ def set_step_scalars(hyper, lr, b1, b2, step):
     """hyper (device, 4 floats) <- {lr, 1 - b1^step, 1 - b2^step, step as uint32}: the one launch of a replayed finetune step that
     carries the per-step scalars by value (include/dp_hip.h dp_set_step_scalars)."""
     assert hyper.is_cuda and hyper.dtype == _f32 and hyper.numel() >= 4 and hyper.is_contiguous()
-    L.check(_lib().dp_set_step_scalars(_p(hyper), lr, 1.0 - b1 ** step, 1.0 - b2 ** step, int(step) & 0xFFFFFFFF, _stream()),
+    L.check(_lib().dp_set_step_scalars(_p(hyper), lr, *bias_corrections(b1, b2, step), int(step) & 0xFFFFFFFF, _stream()),
             'dp_set_step_scalars')
 
 
@@ -1607,8 +1611,7 @@ def adam_ema_dev(p_, g, m, v, ema, coef, hyper, b1, b2, eps, ema_decay):
 
 def adamw_scalars(lr, b1, b2, wd, step):
     """The by-value scalars of dp_adamw_ema as torch.optim.AdamW forms them: Python doubles, rounded to fp32 once by the call."""
-    bc1 = 1.0 - b1 ** step
-    bc2 = 1.0 - b2 ** step
+    bc1, bc2 = bias_corrections(b1, b2, step)
     return dict(p_scale=1.0 - lr * wd, one_minus_b1=1.0 - b1, b2=b2, one_minus_b2=1.0 - b2, sqrt_bc2=bc2 ** 0.5,
                 step_size=lr / bc1)
 

@@ -2,8 +2,9 @@
 
 One step = add_noise -> UNet forward -> eps-loss (sum over C,H,W, mean over the batch) -> hand-written backward
 -> gradient all-reduce (one flat buffer; RCCL over xGMI) -> global-norm clip (1.0) -> Adam -> EMA (constant decay).
-Parameters, gradients, Adam moments and the EMA copy live in flat fp32 buffers so that the optimizer is ONE
-HBM-bound kernel launch (csrc/optim.hip) and the all-reduce is ONE collective.
+Parameters, gradients, Adam moments and the EMA copy live in flat fp32 buffers (train_state.TrainState: the core shared with
+ldm_train -- flat state, accumulation window, exchange ranges, EMA swap) so that the optimizer is ONE HBM-bound kernel launch
+(csrc/optim.hip) and the all-reduce a few collectives over contiguous ranges.  Here: what only this engine has.
 Dropout: the reference finetunes with dropout 0.1 (scripts/finetune_ddpm_cifar10.sh:16 -> utils.set_dropout, utils.py:26-29,
 ddpm_train.py:380-382: EVERY nn.Dropout of the model, i.e. ResnetBlock2D.dropout and Attention.to_out[1]).  The masks are
 Philox functions of (seed, layer, optimizer step, global element index): fused into the GroupNorm+SiLU kernels, regenerated
@@ -21,8 +22,8 @@ import os
 import torch
 
 from . import ops
-from .sweep import StepThrottle, dist_active
-from .train_state import TrainState
+from .sweep import dist_active
+from .train_state import TrainState, flat_views, segment_ranges
 
 
 def antithetic_timesteps(bsz, num_train_timesteps, generator=None):
@@ -215,21 +216,17 @@ class FinetuneEngine(TrainState):
         only.  `last_loss_terms` holds the [kd, eps] device tensor of the last step.
         gradient_accumulation_steps = k: a window of k step() calls is ONE optimizer step on a batch of k * B images per rank,
         sharded in time (see step()).  With k > 1 the step runs eagerly (replay=None resolves to eager, replay=True raises).
-        state_dict() / load_state_dict() (train_state.TrainState) carry the training state; the teacher, the data-loader position
-        and host generators are not part of it and stay with the caller."""
-        k = int(gradient_accumulation_steps)
-        if k < 1 or k != gradient_accumulation_steps:
-            raise ValueError('gradient_accumulation_steps must be a positive integer, got %r' % (gradient_accumulation_steps,))
-        if k > 1 and replay:
-            raise ValueError('replay=True with gradient_accumulation_steps = %d: an accumulating step runs eagerly' % k)
-        self.accum, self._micro = k, 0
+        The flat buffers, the window and state_dict() / load_state_dict() come from train_state.TrainState; the teacher, the
+        data-loader position and host generators are not part of the training state and stay with the caller."""
+        self._init_window(gradient_accumulation_steps, 'gradient_accumulation_steps')
+        if self.accum > 1 and replay:
+            raise ValueError('replay=True with gradient_accumulation_steps = %d: an accumulating step runs eagerly' % self.accum)
         if teacher is not None:
             kd_weights = _check_kd_weights(kd_weights)
             _check_teacher(teacher, model, next(model.parameters()).device)
         self.replay = replay
         self._caps = None            # {capture key: captured step} (_step_replayed)
         self._seen = {}              # {batch shape: eager steps run at it}
-        self._throttle = StepThrottle()
         if dropout is not None:
             set_dropout(model, float(dropout))
         self.model, self.scheduler = model, scheduler
@@ -237,36 +234,14 @@ class FinetuneEngine(TrainState):
         self.dropout_seed = dropout_seed
         self.lr, self.betas, self.eps = lr, betas, eps
         self.ema_decay, self.max_grad_norm, self.group = ema_decay, max_grad_norm, group
-        params = list(model.parameters())
-        dev = params[0].device
+        dev = next(model.parameters()).device
         _require_hip_device(dev)
-        total = sum(p.numel() for p in params)
-        self.flat_p = torch.empty(total, dtype=torch.float32, device=dev)
-        self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        off = 0
-        for p in params:                     # re-home parameters into the flat buffer (views keep nn.Module semantics)
-            n = p.numel()
-            self.flat_p[off:off + n].copy_(p.data.reshape(-1))
-            p.data = self.flat_p[off:off + n].view_as(p)
-            p.grad = self.flat_g[off:off + n].view_as(p)
-            off += n
+        self._init_flat(use_ema)
         # gradient buckets of the data-parallel step: contiguous ranges of the flat gradient buffer that become final at the three
         # milestones of the backward pass (output head + up blocks, mid block, down blocks) and at its end (conv_in, time embedding)
         self._buckets = {'up': [], 'mid': [], 'down': [], 'rest': []}
-        off = 0
-        for name, p in model.named_parameters():
-            seg = ('up' if name.startswith(('up_blocks.', 'conv_norm_out.', 'conv_out.')) else
-                   'mid' if name.startswith('mid_block.') else 'down' if name.startswith('down_blocks.') else 'rest')
-            rs = self._buckets[seg]
-            if rs and rs[-1][1] == off:
-                rs[-1][1] = off + p.numel()
-            else:
-                rs.append([off, off + p.numel()])
-            off += p.numel()
-        self.m = torch.zeros_like(self.flat_p)
-        self.v = torch.zeros_like(self.flat_p)
-        self.ema = self.flat_p.clone() if use_ema else None
-        self.step_count = 0
+        for seg, lo, hi in segment_ranges(self._state_named(), self._segment):
+            self._buckets[seg].append([lo, hi])
         self.acp = scheduler._acp_on(dev)
         self.last_grad_norm = None
         self.teacher, self.kd_weights, self.last_loss_terms = None, None, None
@@ -289,36 +264,29 @@ class FinetuneEngine(TrainState):
                     accumulation=int(self.accum), kd_weights=None if self.kd_weights is None else [float(w) for w in self.kd_weights],
                     use_ema=self.ema is not None)
 
+    @staticmethod
+    def _segment(name):
+        return ('up' if name.startswith(('up_blocks.', 'conv_norm_out.', 'conv_out.')) else
+                'mid' if name.startswith('mid_block.') else 'down' if name.startswith('down_blocks.') else 'rest')
+
     def ema_state(self):
         """EMA parameters as a {name: tensor} dict (views of the flat EMA buffer)."""
-        out, off = {}, 0
-        for n, p in self.model.named_parameters():
-            out[n] = self.ema[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        return out
+        return flat_views(self.ema, self._state_named())
 
     # ---- EMAModel.store / copy_to / restore (training_utils.py:220-262) as used around checkpoints and evaluation
-    #      (ddpm_train.py:387-401,489-514): swap the EMA weights into the live model and back
-    def _weights_changed(self):
-        eng = getattr(self.model, '_engine', None)
-        if eng is not None:
-            eng.packs.clear()                              # packed operands are stale
-
+    #      (ddpm_train.py:387-401,489-514): swap the EMA weights into the live model and back (TrainState._live_*)
     def ema_store(self):
-        self._stash = self.flat_p.clone()
+        self._live_store()
 
     def ema_copy_to(self):
         if self.ema is None:
             raise RuntimeError('FinetuneEngine was built with use_ema=False')
-        self.flat_p.copy_(self.ema)
-        self._weights_changed()
+        self._live_from_shadow()
 
     def ema_restore(self):
-        if getattr(self, '_stash', None) is None:
+        if self._stash is None:
             raise RuntimeError('This ExponentialMovingAverage has no `store()`ed weights to `restore()`')
-        self.flat_p.copy_(self._stash)
-        self._stash = None
-        self._weights_changed()
+        self._live_restore()
 
     REPLAY_OVERLAP = None        # weight-gradient side stream inside the captured step: None = the engine's own rule (by step size)
     # teacher forward on the side stream, beside the student's forward (DP_KD_OVERLAP=0 / 1 overrides).  [measured, C4 shapes,
@@ -358,7 +326,6 @@ class FinetuneEngine(TrainState):
             torch.cuda.current_stream().wait_stream(side)
 
     def _replay_wanted(self, use_dist, dev):
-        import os
         if use_dist or dev.type != 'cuda' or getattr(ops, 'IS_MOCK', False) or not hasattr(ops, 'CapturedCall') or self.accum > 1:
             return False                                 # the data-parallel step interleaves collectives with the backward pass
         if self.replay is None:
@@ -367,7 +334,6 @@ class FinetuneEngine(TrainState):
 
     def _step_replayed(self, clean, noise, timesteps, gb, image_offset):
         """One optimizer step through the captured step (built on first use for this batch shape)."""
-        import os
         model, dev = self.model, self.flat_p.device
         table = getattr(model, 'dropout_table', dict)()
         # everything the captured launches carry as immediate arguments: a change of any of them builds a new capture
@@ -481,7 +447,6 @@ class FinetuneEngine(TrainState):
         use_dist = dist_active(self.group)
         B = clean.shape[0]
         k, j = self.accum, self._micro
-        last = j == k - 1
         gb = global_batch if global_batch is not None else (B * dist.get_world_size(self.group) if use_dist else B) * k
         if image_offset is None:
             image_offset = ((dist.get_rank(self.group) if use_dist else 0) * k + j) * B
@@ -497,12 +462,8 @@ class FinetuneEngine(TrainState):
                                        timesteps.to(device=dev, dtype=torch.long).contiguous(), gb, image_offset)
         clean = clean.to(dev, torch.float32).contiguous()
         noise = noise.to(dev, torch.float32).contiguous()
-        # inside a window the weights did not change: the engine of call 0 and its packed operands are kept (model.engine() drops them)
-        eng = model.engine() if j == 0 or getattr(model, '_engine', None) is None else model._engine
-        eng.bind({n: p.detach() for n, p in model.named_parameters()}, {n: p.grad for n, p in model.named_parameters()})
+        eng = self._window_engine(ops)
         eng.set_dropout(getattr(model, 'dropout_table', dict)(), self.dropout_seed, self.step_count + 1, image_offset)
-        if hasattr(ops, 'pack_weight_batch') and j == 0:
-            eng.prepare_packs()          # the last optimizer step invalidated every packed operand: re-pack in a few launches
         # the batched time-embedding backward finalises the time_emb_proj gradients only at the END of the backward pass: it is
         # switched off when gradient buckets are all-reduced at the segment milestones
         eng.temb_batch = eng.temb_batch and not use_dist
@@ -521,10 +482,9 @@ class FinetuneEngine(TrainState):
             loss, self.last_loss_terms = terms[0:1], terms[1:3]
             del t_out
         pending = []
-        if not last:                                      # the gradient stays in flat_g: no collective, no update, no LR step
+        if j < k - 1:                                     # the gradient stays in flat_g: no collective, no update, no LR step
             eng.backward(dout)
-            self._micro = j + 1
-            self._throttle.mark()
+            self._end_call(last=False)
             return loss
         if use_dist:
             # bucketed all-reduce overlapped with the backward pass: each bucket's collective (RCCL over xGMI) is enqueued as
@@ -545,7 +505,6 @@ class FinetuneEngine(TrainState):
         nc = ops.clip_coef(partial, self.max_grad_norm)
         self.last_grad_norm = nc[0:1]
         self.step_count += 1
-        self._micro = 0
         lr = self.lr_scheduler.get_last_lr()[0] if self.lr_scheduler is not None else self.lr
         self.last_lr = lr
         ops.adam_ema(self.flat_p, self.flat_g, self.m, self.v, self.ema, nc[1:2], lr, self.betas[0], self.betas[1],
@@ -553,5 +512,5 @@ class FinetuneEngine(TrainState):
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()                       # ddpm_train.py:464
         eng.packs.clear()                                  # weights changed: packed operands are stale
-        self._throttle.mark()                              # no host read-back in a step: bound how far the host runs ahead
+        self._end_call(last=True)
         return loss

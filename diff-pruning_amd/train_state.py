@@ -1,6 +1,10 @@
-"""Training state of the finetune engines (train.FinetuneEngine, ldm_train.LdmFinetuneEngine): what a stopped run needs to go on
-bit for bit -- Adam's moments, the EMA shadow, the step counters and the LR schedule -- and the same moments in torch's
-optimizer layout (ddpm_exp/runners/diffusion.py:236-248 `--resume_training`; Lightning's `optimizer_states`).
+"""The flat-buffer core both finetune engines (train.FinetuneEngine, ldm_train.LdmFinetuneEngine) are built on, and their training
+state.  The core: parameters and gradients re-homed into `flat_p` / `flat_g` with the moments and the EMA shadow beside them, the
+accumulation window and the engine a call of it runs on, the ranges of `flat_g` a data-parallel step exchanges (segment_ranges),
+the swap of the live weights against the shadow -- all over ONE offset walk (_offsets).  An engine adds what differs: its step,
+hyper-parameters, segment function, exchange order and EMA rule.  The state: what a stopped run needs to go on bit for bit --
+Adam's moments, the EMA shadow, the step counters and the LR schedule -- and the same moments in torch's optimizer layout
+(ddpm_exp/runners/diffusion.py:236-248 `--resume_training`; Lightning's `optimizer_states`).
 
 The state holds plain tensors, numbers, strings and lists only, so a file of it loads under `weights_only=True`.  NOT part of it:
 the weights themselves (checkpoint.save_training_state writes them beside the state), the frozen teacher of a distillation
@@ -13,15 +17,38 @@ import itertools
 
 import torch
 
+from .sweep import StepThrottle
+
 FORMAT_VERSION = 1
+
+
+def _offsets(named):
+    """(name, parameter, lo, hi) of every parameter in a flat buffer: the one offset walk of the package."""
+    off = 0
+    for n, p in named:
+        yield n, p, off, off + p.numel()
+        off += p.numel()
+
+
+def flat_views(buf, named):
+    """{name: view of `buf` in the parameter's shape}, `named` = [(name, parameter), ...] in the order of the flat buffer."""
+    return {n: buf[lo:hi].view(p.shape) for n, p, lo, hi in _offsets(named)}
 
 
 def param_layout(named):
     """[[name, shape, offset into the flat buffer], ...] in the engine's parameter order."""
-    out, off = [], 0
-    for n, p in named:
-        out.append([n, [int(s) for s in p.shape], off])
-        off += p.numel()
+    return [[n, [int(s) for s in p.shape], lo] for n, p, lo, _ in _offsets(named)]
+
+
+def segment_ranges(named, segment):
+    """[[segment(name), lo, hi], ...] in parameter order, adjacent parameters of one segment merged; the engine orders them."""
+    out = []
+    for n, _, lo, hi in _offsets(named):
+        seg = segment(n)
+        if out and out[-1][0] == seg:
+            out[-1][2] = hi
+        else:
+            out.append([seg, lo, hi])
     return out
 
 
@@ -51,8 +78,9 @@ def _int_step(x):
 
 
 class TrainState:
-    """state_dict / load_state_dict and the torch-layout pair of a finetune engine.  The engine provides flat_p, m, v, ema,
-    step_count, accum (the accumulation factor), _micro (position inside the window) and the three hooks below."""
+    """Base of the finetune engines: the flat state, the accumulation window and state_dict / load_state_dict with their
+    torch-layout pair.  A subclass sets `model`, implements the two hooks below and calls _init_window and _init_flat from its
+    constructor; everything else it reads (flat_p, flat_g, m, v, ema, step_count, accum, _micro) is set up here."""
 
     TORCH_OPTIMIZER = 'Adam'
 
@@ -63,6 +91,68 @@ class TrainState:
     def _state_hyper(self):
         """The hyper-parameters the arithmetic depends on, as plain numbers / lists / None."""
         raise NotImplementedError
+
+    # ---- construction ----------------------------------------------------------------------------------------------------
+    def _init_window(self, k, arg):
+        """accum = k calls of step() are one optimizer step, _micro the position inside the window; `arg` names k in the error."""
+        if int(k) < 1 or int(k) != k:
+            raise ValueError('%s must be a positive integer, got %r' % (arg, k))
+        self.accum, self._micro = int(k), 0
+
+    def _init_flat(self, use_ema, n_shadow=None):
+        """Re-home the parameters of _state_named() into flat_p and bind their gradients to views of flat_g (views keep nn.Module
+        semantics); zeroed moments; with use_ema the shadow of the leading n_shadow elements (default: all of them)."""
+        named = self._state_named()
+        dev = named[0][1].device
+        total = sum(p.numel() for _, p in named)
+        self.flat_p = torch.empty(total, dtype=torch.float32, device=dev)
+        self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
+        for _, p, lo, hi in _offsets(named):
+            self.flat_p[lo:hi].copy_(p.data.reshape(-1))
+            p.data = self.flat_p[lo:hi].view_as(p)
+            p.grad = self.flat_g[lo:hi].view_as(p)
+        self.m = torch.zeros_like(self.flat_p)
+        self.v = torch.zeros_like(self.flat_p)
+        self._n_shadow = total if n_shadow is None else n_shadow
+        self.ema = self.flat_p[:self._n_shadow].clone() if use_ema else None
+        self.step_count = 0
+        self._stash = None
+        self._throttle = StepThrottle()
+
+    # ---- the window ------------------------------------------------------------------------------------------------------
+    def _window_engine(self, ops):
+        """The model's engine for this call, bound to the flat views.  Inside a window the weights did not change: the engine of
+        call 0 and its packed operands are kept (model.engine() drops them); call 0 follows an update that invalidated every
+        operand and re-packs in a few launches.  ops: the engine module's kernel module (a CPU mock has no pack_weight_batch)."""
+        model, first = self.model, self._micro == 0
+        eng = model.engine() if first or getattr(model, '_engine', None) is None else model._engine
+        eng.bind({n: p.detach() for n, p in model.named_parameters()}, {n: p.grad for n, p in model.named_parameters()})
+        if hasattr(ops, 'pack_weight_batch') and first:
+            eng.prepare_packs()
+        return eng
+
+    def _end_call(self, last):
+        """Close a step() call: advance the window; a step reads nothing back, so bound how far the host runs ahead."""
+        self._micro = 0 if last else self._micro + 1
+        self._throttle.mark()
+
+    def _weights_changed(self):
+        eng = getattr(self.model, '_engine', None)
+        if eng is not None:
+            eng.packs.clear()                              # packed operands are stale
+
+    # ---- live weights against the shadow, over the shadow's range (EMAModel / LitEma store, copy_to, restore) ------------------
+    def _live_store(self):
+        self._stash = self.flat_p[:self._n_shadow].clone()
+
+    def _live_from_shadow(self):
+        self.flat_p[:self._n_shadow].copy_(self.ema)
+        self._weights_changed()
+
+    def _live_restore(self):
+        self.flat_p[:self._n_shadow].copy_(self._stash)
+        self._stash = None
+        self._weights_changed()
 
     def _state_counters(self):
         return dict(step_count=int(self.step_count))
@@ -153,13 +243,9 @@ class TrainState:
         writes it: indices in the order of the optimizer's parameter list, `step` a 0-d fp32 tensor, the moments as CPU copies."""
         self._check_window('optimizer_state_dict()')
         named = self._state_named()
-        state, off = {}, 0
-        m, v = self.m.detach().cpu(), self.v.detach().cpu()
-        for i, (_, p) in enumerate(named):
-            n = p.numel()
-            state[i] = dict(step=torch.tensor(float(self.step_count), dtype=torch.float32),
-                            exp_avg=m[off:off + n].clone().view(p.shape), exp_avg_sq=v[off:off + n].clone().view(p.shape))
-            off += n
+        m, v = flat_views(self.m.detach().cpu(), named), flat_views(self.v.detach().cpu(), named)
+        state = {i: dict(step=torch.tensor(float(self.step_count), dtype=torch.float32), exp_avg=m[n].clone(), exp_avg_sq=v[n].clone())
+                 for i, (n, _) in enumerate(named)}
         return dict(state=state, param_groups=[self._torch_param_group(len(named))])
 
     def load_optimizer_state_dict(self, sd):

@@ -376,6 +376,32 @@ def test_ldm_window_shadow_is_updated_every_batch(mocked_ldm):
     assert torch.equal(ft.ema, s - float(omd) * (s - p[:ft.n_unet]))
 
 
+def test_flat_layout_and_exchange_ranges_are_pinned(mocked, mocked_ldm):
+    """The flat layout of both engines at the tiny configs (names, shapes, offsets: tests/golden/flat_layout.json), n_unet, and the
+    ranges of flat_g in the order they go to all_reduce -- DDPM: the buckets of the milestones up, mid, down, then 'rest'; LDM: its
+    sorted list.  Every value was recorded from the engines as they were BEFORE the flat-buffer core moved into train_state
+    (one hand-written offset walk per engine), never from the code under test: a state file or a two-rank run of either side of
+    that move meets the same layout and the same collectives."""
+    ts, want, cfg = pkg('train_state'), load_json('flat_layout.json'), gc.LDM_TINY_CFG
+    ft = pkg('train').FinetuneEngine(pkg('unet').UNet2DModel(**gc.TINY_CFG), pkg('diffusion').DDPMScheduler())
+    assert ts.param_layout(ft._state_named()) == want['ddpm'] and ft.flat_p.numel() == ft.ema.numel() == 2245763
+    assert [(seg, lo, hi) for seg in ('up', 'mid', 'down', 'rest') for lo, hi in ft._buckets[seg]] == [
+        ('up', 661600, 2063328), ('up', 2244832, 2245763), ('mid', 2063328, 2244832), ('down', 21632, 661600), ('rest', 0, 21632)]
+    lf = pkg('ldm_train').LdmFinetuneEngine(pkg('ldm').UNetModel(**cfg), pkg('ldm_sweep').ClassEmbedder(cfg['context_dim'], 1001),
+                                            use_ema=True)
+    assert ts.param_layout(lf._state_named()) == want['ldm'] and lf.flat_p.numel() == 10956435
+    assert lf.n_unet == lf.ema.numel() == 10940419
+    assert [tuple(b) for b in lf._buckets] == [
+        ('output_blocks', 4644640, 10940419), ('middle_block', 3159360, 4644640), ('input_blocks', 20736, 3159360),
+        ('time_embed', 0, 20736), ('cond_stage_model', 10940419, 10956435)]
+    # the views the engines hand out sit at those offsets of their buffers
+    for eng, buf, named in ((ft, ft.flat_p, ft._state_named()), (lf, lf.flat_g, [(n, p.grad) for n, p in lf._state_named()])):
+        for (name, shape, off), (n, t) in zip(ts.param_layout(named), named):
+            assert n == name and tuple(t.shape) == tuple(shape) and t.data_ptr() == buf.data_ptr() + 4 * off
+    offs = {n: off for n, _, off in want['ldm']}
+    assert all(t.data_ptr() == lf.ema.data_ptr() + 4 * offs['model.diffusion_model.' + n] for n, t in lf.ema_state().items())
+
+
 # ---- two ranks -------------------------------------------------------------------------------------------------------
 def _free_port():
     s = socket.socket()

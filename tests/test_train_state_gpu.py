@@ -382,6 +382,69 @@ def test_ema_update_mixed_alignment_takes_the_scalar_path():
     assert names == ['ema_update_kernel<false>'] and torch.equal(a[1:], ref) and not torch.equal(a[1:], s)
 
 
+def _optimizer_operands(n, seed, pad=0, offset=0):
+    """Seeded p, g, m, v (>= 0), shadow as views at element `offset` of device buffers of n + pad elements."""
+    g_ = torch.Generator().manual_seed(seed)
+    host = [torch.randn(n, generator=g_), torch.randn(n, generator=g_), 0.1 * torch.randn(n, generator=g_),
+            torch.rand(n, generator=g_), torch.randn(n, generator=g_)]
+    out = []
+    for h in host:
+        t = torch.full((n + pad,), 777.0, device=DEV)[offset:offset + n]
+        t.copy_(h)
+        out.append(t)
+    return out
+
+
+@pytest.mark.parametrize('n', [1, 255, 257, 1027, 8192 * 256 + 77])
+def test_adam_ema_host_and_device_scalars_agree_bitwise(n):
+    """adam_ema_kernel (lr and the bias corrections by value) and adam_ema_dev_kernel (the same three read from the buffer
+    set_step_scalars fills: the replayed step) run ONE shared device function: the same seeded operands give the same bits in p, m,
+    v and the shadow -- with and without shadow, with and without clip coefficient, at step 1 and 1000.  n: the one-thread grid, both
+    sides of the block edge, a ragged end over several blocks, and a grid-stride turn past the 8192-block cap."""
+    ops = pkg('ops')
+    lr, b1, b2, eps, decay = 2e-4, 0.9, 0.999, 1e-8, 0.9999
+    coef_t = torch.tensor([0.37], device=DEV)
+    hyper = torch.zeros(4, device=DEV)
+    for use_ema in (True, False):
+        for coef in (coef_t, None):
+            for step in (1, 1000):
+                p, g, m, v, s = _optimizer_operands(n, n + step)
+                p2, m2, v2, s2 = p.clone(), m.clone(), v.clone(), s.clone()
+                ops.adam_ema(p, g, m, v, s if use_ema else None, coef, lr, b1, b2, eps, step, decay)
+                ops.set_step_scalars(hyper, lr, b1, b2, step)
+                ops.adam_ema_dev(p2, g, m2, v2, s2 if use_ema else None, coef, hyper, b1, b2, eps, decay)
+                torch.cuda.synchronize()
+                assert int(hyper.view(torch.int32)[3]) == step
+                for name, a, b in (('p', p, p2), ('m', m, m2), ('v', v, v2), ('ema', s, s2)):
+                    assert torch.equal(a, b), (name, use_ema, coef is not None, step)
+                assert bool(torch.isfinite(p).all())
+
+
+@pytest.mark.parametrize('d', ['warmup', 0.9999])
+@pytest.mark.parametrize('offset', [0, 1])
+@pytest.mark.parametrize('n', [1, 3, 4, 1027])
+def test_fused_and_standalone_litema_agree_bitwise(n, offset, d):
+    """One AdamW step with the LitEma shadow fused in == the same step without a shadow followed by dp_ema_update, bit for bit in
+    the shadow and in p, m, v: both kernels call the one dp_lit_ema of csrc/dp_common.h (the guarantee the header of csrc/ema.hip
+    states).  Element offset 0 with n >= 4 takes the 16-byte path of both kernels, everything else the 4-byte path; d: the first
+    warm-up decay of lit_ema_decay (2/11 in fp32) and the cap."""
+    ops = pkg('ops')
+    d = pkg('ldm_train').lit_ema_decay(0.9999, 1) if d == 'warmup' else d
+    args = (1.28e-4, 0.9, 0.999, 1e-8, 1e-2, 3)
+    p, g, m, v, s = _optimizer_operands(n, 17 * n + offset, pad=5, offset=offset)
+    p2, g2, m2, v2, s2 = _optimizer_operands(n, 17 * n + offset, pad=5, offset=offset)
+    assert torch.equal(p, p2) and torch.equal(s, s2)
+    vec = 'true' if offset == 0 and n >= 4 else 'false'
+    assert _launched(ops, lambda: ops.adamw_ema(p, g, m, v, s, *args, ema_decay=d)) == ['adamw_ema_kernel<%s>' % vec]
+    names = _launched(ops, lambda: (ops.adamw_ema(p2, g2, m2, v2, None, *args), ops.ema_update(s2, p2, d)))
+    assert names == ['adamw_ema_kernel<%s>' % vec, 'ema_update_kernel<%s>' % vec]
+    torch.cuda.synchronize()
+    for name, a, b in (('shadow', s, s2), ('p', p, p2), ('m', m, m2), ('v', v, v2)):
+        assert torch.equal(a, b), name
+    p0, _, _, _, s0 = _optimizer_operands(n, 17 * n + offset)
+    assert not torch.equal(p, p0) and not torch.equal(s, s0)          # both moved
+
+
 # ---- torch's optimizer layout ----------------------------------------------------------------------------------------
 def test_torch_adam_loads_the_exported_state_and_steps_alike(report):
     """torch.optim.Adam loads optimizer_state_dict(); one torch step on clones with the engine's next (clipped) gradient lands within
