@@ -153,6 +153,8 @@ SIGNATURES = {
     'dp_adam_ema_dev': [_vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _f, _f, _f, _f, _vp],
     'dp_ddim_step': [_vp, _vp, _vp, _f, _f, _f, _i, _f, _vp, _ll, _vp],
     'dp_ddpm_step': [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, _ll, _vp],
+    'dp_denoise_step': [_vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _ll, _vp],
+    'dp_image_to_u8': [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp],
     'dp_dropout_apply': [_vp, _ll, _vp, _ll, _i, _ll, _dr, _vp],
     'dp_dropout_mask': [_vp, _ll, _ll, _dr, _vp],
     'dp_layernorm_fwd': [_vp, _ll, _vp, _vp, _i, _i, _i, _f, _vp, _ll, _vp, _vp],

@@ -1685,6 +1685,46 @@ def ddpm_step(x, eps, sqrt_a_t, sqrt_b_t, c_x0, c_xt, sigma=0.0, vnoise=None, cl
     return out
 
 
+DENOISE_GENERALIZED, DENOISE_DDPM = 0, 1
+DENOISE_MAX_BLOCKS = 4096            # DP_DENOISE_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
+
+
+def denoise_step(x, eps, mode, coef, z=None, out=None, x0_out=None):
+    """One ddpm_exp sampler update (dp_denoise_step, csrc/sampler.hip) over flat fp32 data.  `coef`: the host's fp32 scalars --
+    mode DENOISE_GENERALIZED (s1, s2, s3, c1, c2): x0 = (x - eps s1) / s2, next = s3 x0 + c1 z + c2 eps;
+    mode DENOISE_DDPM (r1, r2, k0, kx, d, sig): x0 = clamp(r1 x - r2 eps, -1, 1), next = (k0 x0 + kx x) / d + sig z.
+    z None: no noise term.  `out` may be `x`; `x0_out` (written in the same pass when given) aliases nothing.  Returns `out`."""
+    assert x.dtype == _f32 and eps.dtype == _f32 and x.is_contiguous() and eps.is_contiguous() and eps.numel() == x.numel()
+    assert z is None or (z.dtype == _f32 and z.is_contiguous() and z.numel() == x.numel())
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == _f32 and out.is_contiguous() and out.numel() == x.numel()
+    if x0_out is not None:
+        assert x0_out.dtype == _f32 and x0_out.is_contiguous() and x0_out.numel() == x.numel()
+        assert x0_out.data_ptr() not in (x.data_ptr(), out.data_ptr(), eps.data_ptr())
+    c = [float(v) for v in coef]
+    assert len(c) == (5 if mode == DENOISE_GENERALIZED else 6)
+    c += [0.0] * (6 - len(c))
+    L.check(_lib().dp_denoise_step(_p(x), _p(eps), _p(z), int(mode), c[0], c[1], c[2], c[3], c[4], c[5], _p(out), _p(x0_out),
+                                   x.numel(), _stream()), 'dp_denoise_step')
+    return out
+
+
+def image_to_u8(x, rescaled=True, out=None):
+    """fp32 [N, C, H, W] (free image stride) -> uint8 [N, H, W, C] (dp_image_to_u8, the inverse of dp_u8_to_float):
+    (unsigned char) clamp(v * 255 + 0.5, 0, 255) with v = clamp((x + 1) / 2, 0, 1) when `rescaled`, else clamp(x, 0, 1) --
+    inverse_data_transform followed by save_image's byte conversion, equal to the torch fp32 expression bit for bit.
+    torchvision is absent from the build machine and from the reference tree: save_image's formula is recalled, and parity with
+    torchvision itself is unpinned."""
+    s = _chk_act(x)
+    N, Cc, H, W = x.shape
+    if out is None:
+        out = torch.empty((N, H, W, Cc), dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (N, H, W, Cc)
+    L.check(_lib().dp_image_to_u8(_p(x), s, N, Cc, H, W, 1 if rescaled else 0, _p(out), _stream()), 'dp_image_to_u8')
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # LDM transformer-block glue (channel-major tokens [N, C, H, W] == [N][C][T])
 # --------------------------------------------------------------------------------------------------

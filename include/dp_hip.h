@@ -406,6 +406,27 @@ int dp_ddim_step(const float* x, const float* eps, const float* vnoise, float a_
 int dp_ddpm_step(const float* x, const float* eps, const float* vnoise, float sqrt_a_t, float sqrt_b_t, float c_x0,
                  float c_xt, float sigma, int clip, float clip_range, float* out, long long n, void* stream);
 
+/* One update of the ddpm_exp sampler (csrc/sampler.hip; ddpm_exp/functions/denoising.py) over n fp32 elements, one pass:
+ *   mode 0, generalized_steps:23-29:  x0 = (x - eps * p0) / p1;              next = p2 * x0 + p3 * z + p4 * eps
+ *           (p0 .. p4 = sqrt(1 - a_t), sqrt(a_t), sqrt(a_next), c1, c2; p5 unread)
+ *   mode 1, ddpm_steps:53-65:         x0 = clamp(p0 * x - p1 * eps, -1, 1);  next = (p2 * x0 + p3 * x) / p4 + p5 * z
+ *           (p0 .. p5 = sqrt(1 / a_t), sqrt(1 / a_t - 1), sqrt(a_next) * beta_t, sqrt(1 - beta_t) * (1 - a_next), 1 - a_t, sigma)
+ * every operation rounded separately, in the reference's order, with a true division; the scalars are the host's 0-d fp32
+ * arithmetic.  z == NULL: no noise term (eta = 0, where c1 is exactly 0; the t = 0 mask).  x0_out != NULL: the x0 prediction is
+ * written in the same pass.  `next` may be `x`; x0_out aliases nothing.  16-byte accesses between a scalar head and tail when all
+ * pointers share one alignment modulo 16, 4-byte accesses otherwise; any n (long long indexing, grid-stride beyond
+ * DP_DENOISE_MAX_BLOCKS blocks of 256 lanes). */
+#define DP_DENOISE_MAX_BLOCKS 4096
+int dp_denoise_step(const float* x, const float* eps, const float* z, int mode, float p0, float p1, float p2, float p3, float p4,
+                    float p5, float* next, float* x0_out, long long n, void* stream);
+/* fp32 x [N][C][H][W] (image stride x_img_stride floats) -> uint8 out [N][H][W][C], the inverse of dp_u8_to_float:
+ *   v = rescaled ? clamp((x + 1) / 2, 0, 1) : clamp(x, 0, 1)      (inverse_data_transform, ddpm_exp/datasets/__init__.py:177-186)
+ *   out = (unsigned char) clamp(v * 255 + 0.5, 0, 255), the multiply and the add rounded separately: the torch fp32 expression
+ *   bit for bit.  torchvision is absent from the build machine and from the reference tree: save_image's formula is recalled,
+ *   and parity with torchvision itself is unpinned. */
+int dp_image_to_u8(const float* x, long long x_img_stride, int N, int C, int H, int W, int rescaled, unsigned char* out,
+                   void* stream);
+
 /* ---- LDM (CompVis) transformer-block glue on channel-major tokens x[n][c][t]  (ldm_exp/ldm/modules/attention.py) ---- */
 /* LayerNorm over the C channels of every token (attention.py:200-212 norm1/2/3); stats[(n*T+t)*2+{0,1}] = {mean, rstd}. */
 int dp_layernorm_fwd(const float* x, long long x_img_stride, const float* gamma, const float* beta, int N, int C, int T,
