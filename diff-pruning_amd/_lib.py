@@ -74,6 +74,12 @@ class PackItem(C.Structure):
                 ('ld', C.c_int), ('blk0', C.c_int), ('nblk', C.c_int), ('_pad', C.c_int)]
 
 
+class Ups9Params(C.Structure):
+    _fields_ = [('U', C.c_void_p), ('dy', C.c_void_p), ('dx', C.c_void_p), ('dy_img_stride', LL), ('dx_img_stride', LL),
+                ('u_bytes', C.c_uint), ('dy_bytes', C.c_uint)] + [(n, C.c_int) for n in ('ldu', 'N', 'M', 'K', 'H', 'W',
+                                                                                         'accumulate', 'tile')]
+
+
 class ColsumItem(C.Structure):
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('N', C.c_int), ('C', C.c_int), ('wstride', C.c_int),
                 ('woff', C.c_int), ('accumulate', C.c_int), ('ld', C.c_int)]
@@ -139,6 +145,9 @@ SIGNATURES = {
     'dp_deinterleave2x2': [_vp, _ll, _i, _i, _i, _i, _vp, _ll, _ll, _vp],
     'dp_ups_weff': [_vp, _ll, _vp, _vp],
     'dp_ups_wfold': [_vp, _ll, _vp, _i, _vp],
+    'dp_ups9_u': [_vp, _ll, _vp, _vp],
+    'dp_ups9_dgrad': [C.POINTER(Ups9Params), _vp],
+    'dp_ups9_dgrad_supported': [C.POINTER(Ups9Params)],
     'dp_wg_reduce': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp],
     'dp_gather_add': [_vp, _vp, _i, _vp, _vp],
     'dp_group_score': [C.POINTER(ScoreMember), _i, _i, _vp, _vp, _vp, _vp],

@@ -102,6 +102,9 @@ class _Packs:
             buf, ld = ops.pack_weight_wino(w, mode[1])
         elif isinstance(mode, tuple) and mode[0] == 'wino2d':  # ('wino2d', 0 | 1): Winograd F(2x2, 3x3) operand (ops.pack_weight_wino2d)
             buf, ld = ops.pack_weight_wino2d(w, mode[1])
+        elif isinstance(mode, tuple) and mode[0] == 'up9':     # ('up9', 0, 1): dgrad operand of U = G w G^T (ops.ups9_u, csrc/ups9.hip)
+            self.lazy[(name, mode)] = True
+            buf, ld = ops.pack_weight(self.get_u9(name, w), mode[2])
         elif isinstance(mode, tuple) and mode[0] == 'up':      # ('up', class, 0 | 1): class kernel of an upsample convolution
             self.lazy[(name, mode)] = True
             weff = self.get_weff(name, w)
@@ -130,6 +133,17 @@ class _Packs:
         weff = ops.ups_weff(w)
         self._c[key] = (tag, weff, 0)
         return weff
+
+    def get_u9(self, name, w):
+        """U[Cout, Cin, 3, 3] = G w G^T of the upsample convolution `name` (ops.ups9_u), cached like the packs."""
+        key = (name, 'u9')
+        tag = (w.data_ptr(), w._version, tuple(w.shape))
+        hit = self._c.get(key)
+        if hit is not None and hit[0] == tag:
+            return hit[1]
+        u = ops.ups9_u(w)
+        self._c[key] = (tag, u, 0)
+        return u
 
     def clear(self):
         self._c.clear()
@@ -374,8 +388,8 @@ class UNetEngine:
                     w = self.P.get(name + '.weight')
                     if w is None or self.packs.has(name, w, what):
                         continue
-                    weff = self.packs.get_weff(name, w)
-                    derived.append((lambda buf, ld, name=name, w=w, what=what: self.packs.put(name, w, what, buf, ld), weff[what[1]], what[2]))
+                    src = self.packs.get_u9(name, w) if what[0] == 'up9' else self.packs.get_weff(name, w)[what[1]]
+                    derived.append((lambda buf, ld, name=name, w=w, what=what: self.packs.put(name, w, what, buf, ld), src, what[2]))
         if hasattr(ops, 'pack_weight_batch') and (todo or derived) and all(w.is_contiguous() for _, w, _ in todo):
             packed = ops.pack_weight_batch([(w, mode) for _, w, mode in todo] + [(w, m) for _, w, m in derived])
             for (name, w, mode), (buf, ld) in zip(todo, packed):
@@ -536,12 +550,17 @@ class UNetEngine:
         """Accumulate the weight / bias gradients of the upsample convolution `name`; return the gradient w.r.t. its
         low-resolution input x (what Upsample2D's autograd returns after the 2x2 sum of UpsampleNearest2DBackward)."""
         w = self.P[name + '.weight']
-        dyq = ops.deinterleave2x2(dy)
+        # the input gradient in nine products per pixel straight from the high-resolution dy (csrc/ups9.hip) where the gate takes the
+        # shape: the class kernels below then serve the weight gradient alone, and their de-interleave pass moves to its stream
+        use9 = hasattr(ops, 'ups9_dgrad_wanted') and ops.ups9_dgrad_wanted(x.shape[0], w.shape[1], w.shape[0], x.shape[2], x.shape[3])
+        dyq = None if use9 else ops.deinterleave2x2(dy)
         rows = None
         if (name + '.bias') in self.P and self._rows_src is not None and self._rows_src[0].data_ptr() == dy.data_ptr():
             rows = self._rows_of(dy)
 
-        def param_grads(rows):
+        def param_grads(rows, dyq=dyq):
+            if dyq is None:
+                dyq = ops.deinterleave2x2(dy)
             gweff = torch.empty((4,) + tuple(w.shape[:2]) + (2, 2), dtype=torch.float32, device=dy.device)
             for c, spec in enumerate(_UPS_SPECS):
                 ops.conv_wgrad(dyq[c], x, None, gweff[c], spec, accumulate=False)
@@ -551,12 +570,15 @@ class UNetEngine:
                     rows = ops.rowsum_nc(dy)
                 self._colsum(rows, rows.shape[0], rows.shape[1], 1, 0, self.G[name + '.bias'])
 
-        side = self._side_stream(dyq, dy, x, rows)
+        side = self._side_stream(dy, dyq, x, rows)
         if side is None:
             param_grads(rows)
         else:
             with torch.cuda.stream(side):
                 param_grads(rows)
+        if use9:
+            up, ldu = self.packs.get(name, w, ('up9', 0, 1))
+            return ops.ups9_dgrad(dy, up, ldu, w.shape[1])
         dx = None
         for c, spec in enumerate(_UPS_SPECS):
             wd, ldd = self.packs.get(name, w, ('up', c, 1))

@@ -772,8 +772,106 @@ def ups_wfold(gweff, gw, accumulate=True):
     return gw
 
 
+# ---- Upsample2D's convolution in 9 multiplies per low-resolution pixel and channel pair (csrc/ups9.hip): the input gradient
+UPS9 = os.environ.get('DP_UPS9', '1') not in ('0', '')      # DP_UPS9=0: the four class launches everywhere
+UPS9_TILE_PIX = (32, 64, 128)                                # pixels per workgroup of dp_ups9_params.tile 0 / 1 / 2
+_UPS9_NAMES = ('ups9_dgrad_kernel<128, 32, 8, 4, 1, 2>', 'ups9_dgrad_kernel<128, 64, 4, 2, 2, 3>', 'ups9_dgrad_kernel<128, 128, 4, 2, 2, 2>')
+UPS9_GATE_MIN_BLOCKS, UPS9_GATE_MAX_CH = 128, 256            # (see ups9_dgrad_gate)
+UPS9_MIN_BLOCKS = 512                                        # pick the widest tile that still gives two workgroups per CU
+
+
+def ups9_u(w):
+    """U[Cout, Cin, 3, 3] = G w G^T, G = [1 0 0; 1 1 1; 0 0 1] (dp_ups9_u): the nine-product kernel of `upsample x2 -> conv3x3(w)`."""
+    assert w.dim() == 4 and w.shape[2:] == (3, 3) and w.is_contiguous()
+    u = torch.empty_like(w)
+    L.check(_lib().dp_ups9_u(_p(w), w.shape[0] * w.shape[1], _p(u), _stream()), 'dp_ups9_u')
+    return u
+
+
+def ups9_tile(N, Cin, H, W):
+    """The widest pixel tile whose grid still has UPS9_MIN_BLOCKS workgroups (else the narrowest)."""
+    npix, mt = N * H * W, (Cin + 127) // 128
+    for t in (2, 1):
+        if -(-npix // UPS9_TILE_PIX[t]) * mt >= UPS9_MIN_BLOCKS:
+            return t
+    return 0
+
+
+def ups9_dgrad_shape_ok(N, Cin, Cout, H, W, dy_img_stride, dx_img_stride, dy_bytes, ldu, u_bytes, tile, u_ptr=0):
+    """The same rule as dp_ups9_dgrad_supported (csrc/ups9.hip), argument by argument, so that a launch is never refused natively
+    after the host chose it.  H, W: the LOW resolution; strides in floats, extents in bytes."""
+    if min(N, Cin, Cout, H, W) < 1 or tile not in (0, 1, 2) or (u_ptr & 15):
+        return False
+    if ldu < Cin or (ldu & 3):
+        return False
+    HW = H * W
+    npix = HW * N
+    if npix >= (1 << 29):
+        return False
+    if 9 * Cout * ldu * 4 != u_bytes or u_bytes >= _MAX_BYTES:
+        return False
+    if dy_img_stride < 4 * HW * Cout or dx_img_stride < HW * Cin:
+        return False
+    if dy_bytes < ((N - 1) * dy_img_stride + 4 * HW * Cout) * 4 or dy_bytes >= _MAX_BYTES:
+        return False
+    return -(-npix // UPS9_TILE_PIX[tile]) * ((Cin + 127) // 128) < (1 << 31)
+
+
+def ups9_dgrad_gate(N, Cin, Cout, H, W):
+    """Shape classes on which dp_ups9_dgrad beat the four class launches it replaces (tools/bench_ups9.py, profiles/ups9_gate.txt);
+    everything else keeps the class launches.  [measured, ms per call, four class launches -> dp_ups9_dgrad: batch 256 x 256 channels 0.156 -> 0.068
+    (4x4), 0.323 -> 0.214 (8x8), 1.030 -> 0.716 (16x16); pruned 180 channels x batch 128: 0.086 -> 0.049, 0.162 -> 0.085, 0.345 -> 0.263; bedroom256's 4
+    images: 256 ch @ 32x32 0.147 -> 0.068, @ 64x64 0.325 -> 0.211, 128 ch @ 128x128 0.304 -> 0.191; but 512 ch @ 8x8 0.114 -> 0.133 (32 workgroups) and
+    @ 16x16 0.138 -> 0.131 (128 workgroups, a tie, and 3.0e-6 of fp32 error): hence at most 256 channels and at least 128 workgroups.]"""
+    blocks32 = -(-(N * H * W) // 32) * ((Cin + 127) // 128)
+    return blocks32 >= UPS9_GATE_MIN_BLOCKS and max(Cin, Cout) <= UPS9_GATE_MAX_CH
+
+
+def ups9_dgrad_wanted(N, Cin, Cout, H, W):
+    """Host gate of the nine-product input gradient: DP_UPS9 and the measured (shape class) table below.  Shapes only -- the
+    caller's tensors are checked again, strides and extents included, by ups9_dgrad_shape_ok at the launch."""
+    if not UPS9 or min(N, Cin, Cout, H, W) < 1 or N * H * W * 4 * Cout * 4 >= _MAX_BYTES:
+        return False
+    return ups9_dgrad_gate(N, Cin, Cout, H, W)
+
+
+def _ups9_params(dy, up, ldu, Cin, out, accumulate, tile):
+    sd, so = _chk_act(dy), _chk_act(out)
+    N, Cout, H2, W2 = dy.shape
+    p = L.Ups9Params()
+    p.U, p.dy, p.dx = _p(up), _p(dy), _p(out)
+    p.dy_img_stride, p.dx_img_stride = sd, so
+    p.u_bytes, p.dy_bytes = up.numel() * 4, _extent_bytes(dy)
+    p.ldu, p.N, p.M, p.K, p.H, p.W = ldu, N, Cin, Cout, H2 // 2, W2 // 2
+    p.accumulate, p.tile = 1 if accumulate else 0, tile
+    return p
+
+
+def ups9_dgrad(dy, up, ldu, Cin, *, out=None, accumulate=False, tile=None):
+    """Gradient w.r.t. the LOW-resolution input of `upsample x2 -> conv3x3` from the high-resolution dy[N, Cout, 2H, 2W].
+    up / ldu: pack_weight(ups9_u(w), 1).  Raises when the shape rule refuses the launch (callers ask ups9_dgrad_wanted first)."""
+    N, Cout, H2, W2 = dy.shape
+    assert H2 % 2 == 0 and W2 % 2 == 0
+    H, W = H2 // 2, W2 // 2
+    if out is None:
+        assert not accumulate
+        out = empty_act((N, Cin, H, W), dy.device)
+    assert out.shape == (N, Cin, H, W)
+    if tile is None:
+        tile = ups9_tile(N, Cin, H, W)
+    p = _ups9_params(dy, up, ldu, Cin, out, accumulate, tile)
+    ok = ups9_dgrad_shape_ok(N, Cin, Cout, H, W, p.dy_img_stride, p.dx_img_stride, p.dy_bytes, ldu, p.u_bytes, tile, up.data_ptr())
+    assert ok == bool(_lib().dp_ups9_dgrad_supported(C.byref(p))), 'host shape rule and dp_ups9_dgrad_supported disagree'
+    if not ok:
+        raise ValueError('dp_ups9_dgrad does not take this launch (ups9_dgrad_shape_ok)')
+    L.check(_run(lambda: _lib().dp_ups9_dgrad(C.byref(p), _stream()),
+                 _UPS9_NAMES[tile],
+                 2.0 * Cin * N * H * W * Cout * 9, 4.0 * (dy.numel() + up.numel() + out.numel())), 'dp_ups9_dgrad')
+    return out
+
+
 _ws_cache = {}
-WGRAD_BLOCKS = 1024          # target workgroups per wgrad launch (256 CUs x 4 resident workgroups)
+WGRAD_BLOCKS = 1024         # target workgroups per wgrad launch (256 CUs x 4 resident workgroups)
 WGRAD_MIN_PIX = int(os.environ.get('DP_WGRAD_MIN_PIX', '128'))      # fewest pixels per split-K slice of a weight gradient
 
 

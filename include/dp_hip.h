@@ -329,6 +329,26 @@ int dp_deinterleave2x2(const float* y, long long y_img_stride, int N, int C, int
 int dp_ups_weff(const float* w, long long M, float* weff, void* stream);
 int dp_ups_wfold(const float* gweff, long long M, float* gw, int accumulate, void* stream);
 
+/* The same Upsample2D convolution in NINE multiplies per low-resolution pixel and channel pair (csrc/ups9.hip):
+ * U = G w G^T per (co, ci), G = [1 0 0; 1 1 1; 0 0 1] (dp_ups9_u: u[M][3][3] from w[M][3][3], M = Cout*Cin).
+ * dp_ups9_dgrad: dx[n][ci][i][j] (+)= sum_co sum_{a,b} U[co][ci][a][b] T[a][b], T = R p R^T of the 4x4 patch p of the
+ * high-resolution dy[N][K][2H][2W] at rows 2i-1 .. 2i+2 / columns 2j-1 .. 2j+2 (zero outside), R = [0 -1 0 1; 0 1 1 0; 1 0 -1 0]:
+ * the gradient w.r.t. the LOW-resolution input, read from dy as it is (no de-interleave pass).
+ * U: dp_pack_weight(u, mode 1) -- exactly 9 * K * ldu floats, 16-byte aligned; M = Cin, K = Cout; H, W: the low resolution.
+ * dy / dx: contiguous images at dy_img_stride / dx_img_stride floats; dy_bytes: readable extent from dy, below 2 GiB.
+ * tile: pixels per workgroup, 0 = 32 (8 channels per K tile), 1 = 64, 2 = 128 (4 channels): one fixed-order sum per output, the
+ * same bits from run to run; tiles 1 and 2 sum in the same order, tile 0 in its own.
+ * dp_ups9_dgrad returns hipErrorInvalidValue for what dp_ups9_dgrad_supported refuses. */
+typedef struct dp_ups9_params {
+    const float* U; const float* dy; float* dx;
+    long long dy_img_stride, dx_img_stride;
+    unsigned u_bytes, dy_bytes;
+    int ldu, N, M, K, H, W, accumulate, tile;
+} dp_ups9_params;
+int dp_ups9_u(const float* w, long long M, float* u, void* stream);
+int dp_ups9_dgrad(const dp_ups9_params* p, void* stream);
+int dp_ups9_dgrad_supported(const dp_ups9_params* p);
+
 /* Taylor-importance reductions  (ddpm_exp/torch_pruning/importance.py:375-434).
  * Weight viewed as [R][C][T]; dim = 0: out[r] = sum_{c,t} f(w*g); dim = 1: out[c] = sum_{r,t} f(w*g);
  * mode 0: f = (w g)^2 (vendored), mode 1: f = |w g| (sum_abs), mode 2: signed sum then |.| (abs_sum),
