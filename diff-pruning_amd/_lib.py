@@ -164,6 +164,7 @@ SIGNATURES = {
     'dp_ddpm_step': [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, _ll, _vp],
     'dp_denoise_step': [_vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _ll, _vp],
     'dp_image_to_u8': [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp],
+    'dp_cfg_denoise_step': [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp],
     'dp_dropout_apply': [_vp, _ll, _vp, _ll, _i, _ll, _dr, _vp],
     'dp_dropout_mask': [_vp, _ll, _ll, _dr, _vp],
     'dp_layernorm_fwd': [_vp, _ll, _vp, _vp, _i, _i, _i, _f, _vp, _ll, _vp, _vp],

@@ -1823,6 +1823,44 @@ def image_to_u8(x, rescaled=True, out=None):
     return out
 
 
+CFG_ORDER_PLAIN, CFG_ORDER_AB2, CFG_ORDER_AB3, CFG_ORDER_AB4, CFG_ORDER_EULER = 0, 1, 2, 3, 4
+
+
+def cfg_denoise_step(x, e, coef, scale=None, order=0, hist=(), z=None, temperature=1.0, out=None, x0_out=None, eg_out=None):
+    """One model evaluation of the ldm_exp samplers (dp_cfg_denoise_step, csrc/ldm_sampler.hip) over flat fp32 data.
+    `e`: with `scale` given, the [2B, ...] eps of forward_cfg_pair -- unconditional half first, read in place -- and
+    e_g = e_u + scale (e_c - e_u); with scale None the model's one output, e_g = e.  `order` / `hist` (newest first): e' = e_g |
+    (3 e_g - h1) / 2 | (23 e_g - 16 h1 + 5 h2) / 12 | (55 e_g - 59 h1 + 37 h2 - 9 h3) / 24 | (h1 + e_g) / 2.
+    `coef` = (s1m, sqrt_a_t, sqrt_a_prev, c_dir, sigma), the host's fp32 scalars: x0 = (x - s1m e') / sqrt_a_t,
+    next = (sqrt_a_prev x0 + c_dir e') + (sigma z) temperature; z None: no noise term.  `out` may be `x`; `x0_out` and `eg_out`
+    (written in the same pass when given) alias nothing.  Returns `out`."""
+    n = x.numel()
+    guided = scale is not None
+    assert x.dtype == _f32 and e.dtype == _f32 and x.is_contiguous() and e.is_contiguous() and e.numel() == (2 * n if guided else n)
+    assert z is None or (z.dtype == _f32 and z.is_contiguous() and z.numel() == n)
+    need = (0, 1, 2, 3, 1)[order]
+    hist = list(hist)[:need]
+    assert len(hist) == need and all(h.dtype == _f32 and h.is_contiguous() and h.numel() == n for h in hist)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == _f32 and out.is_contiguous() and out.numel() == n
+    ins = [x.data_ptr(), e.data_ptr()] + [h.data_ptr() for h in hist] + ([z.data_ptr()] if z is not None else [])
+    assert out.data_ptr() not in ins[1:]
+    for o in (x0_out, eg_out):
+        if o is not None:
+            assert o.dtype == _f32 and o.is_contiguous() and o.numel() == n
+            assert o.data_ptr() not in ins and o.data_ptr() != out.data_ptr()
+    assert x0_out is None or eg_out is None or x0_out.data_ptr() != eg_out.data_ptr()
+    c = [float(v) for v in coef]
+    assert len(c) == 5
+    e_c = C.c_void_p(e.data_ptr() + 4 * n) if guided else None
+    h = [_p(t) for t in hist] + [None] * (3 - need)
+    L.check(_lib().dp_cfg_denoise_step(_p(x), _p(e), e_c, float(scale) if guided else 1.0, int(order), h[0], h[1], h[2], c[0], c[1],
+                                       c[2], c[3], c[4], float(temperature), _p(z), _p(out), _p(x0_out), _p(eg_out), n, _stream()),
+            'dp_cfg_denoise_step')
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # LDM transformer-block glue (channel-major tokens [N, C, H, W] == [N][C][T])
 # --------------------------------------------------------------------------------------------------

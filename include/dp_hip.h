@@ -447,6 +447,26 @@ int dp_denoise_step(const float* x, const float* eps, const float* z, int mode, 
 int dp_image_to_u8(const float* x, long long x_img_stride, int N, int C, int H, int W, int rescaled, unsigned char* out,
                    void* stream);
 
+/* One model evaluation of the ldm_exp samplers (csrc/ldm_sampler.hip; ldm_exp/ldm/models/diffusion/ddim.py:165-203 and
+ * plms.py:173-236) over n fp32 elements, one pass, in the reference's operation order:
+ *   e_g  = e_u + scale * (e_c - e_u)                 e_c == NULL: the unguided path, e_g = e_u.  With the [2B, C, H, W] eps of
+ *                                                    forward_cfg_pair, e_c = e_u + n: both halves are read in place
+ *   e'   = e_g                                       order 0
+ *        | (3 e_g - h1) / 2                          order 1   (h1 the newest stored guided eps, h3 the oldest)
+ *        | (23 e_g - 16 h1 + 5 h2) / 12              order 2
+ *        | (55 e_g - 59 h1 + 37 h2 - 9 h3) / 24      order 3
+ *        | (h1 + e_g) / 2                            order 4   (PLMS's first step: h1 = e_t, e_g = e_t_next)
+ *   x0   = (x - s1m * e') / sqrt_a_t
+ *   next = (sqrt_a_prev * x0 + c_dir * e') + (sigma * z) * temperature          z == NULL: no noise term
+ * every operation rounded separately, true divisions; the scalars are the host's (ldm_sampler.sampling_tables).  x0_out / eg_out
+ * != NULL: the x0 prediction / the guided eps e_g are written in the same pass.  `next` may be `x`; x0_out and eg_out alias
+ * nothing.  A history pointer the order does not read may be NULL.  16-byte accesses between a scalar head and tail when all
+ * pointers in use share one alignment modulo 16, 4-byte accesses otherwise; any n (long long indexing, grid-stride beyond
+ * DP_DENOISE_MAX_BLOCKS blocks of 256 lanes). */
+int dp_cfg_denoise_step(const float* x, const float* e_u, const float* e_c, float scale, int order, const float* h1, const float* h2,
+                        const float* h3, float s1m, float sqrt_a_t, float sqrt_a_prev, float c_dir, float sigma, float temperature,
+                        const float* z, float* next, float* x0_out, float* eg_out, long long n, void* stream);
+
 /* ---- LDM (CompVis) transformer-block glue on channel-major tokens x[n][c][t]  (ldm_exp/ldm/modules/attention.py) ---- */
 /* LayerNorm over the C channels of every token (attention.py:200-212 norm1/2/3); stats[(n*T+t)*2+{0,1}] = {mean, rstd}. */
 int dp_layernorm_fwd(const float* x, long long x_img_stride, const float* gamma, const float* beta, int N, int C, int T,
