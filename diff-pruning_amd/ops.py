@@ -4,6 +4,22 @@ Every function enqueues HIP kernels on torch's current stream and returns immedi
 for allocation only.  Activations are 4-D [N, C, H, W] fp32 tensors whose inner three strides are
 contiguous (stride(1) == H*W) while stride(0) -- the image stride -- is free, so channel slices of a
 larger buffer are passed without copies.
+
+The Winograd routes of a 3x3 / stride 1 / pad 1 convolution (_WINO_ROUTES, one launch body: _conv_wino_route; a route is taken when
+its switch is on, the grid rule _wino_splits says yes and the library's `*_supported` takes the block, else the next form follows):
+
+  route        kernel file     switch  min tiles         tile (rows x pixels)  K tiles (n_iter)         multiplies  follows when refused
+  F(4, 3)      winograd43.hip  WINO43  WINO43_MIN_TILES  64 x 256              3 * (C // 8)             4.5 of 9    F(2, 3) / F(2x2, 3x3)
+  F(2x2, 3x3)  winograd2d.hip  WINO2D  WINO2D_MIN_TILES  64 x 128              C // 8                   4 of 9      the direct form
+  F(2, 3)      winograd.hip    WINO    WINO_MIN_TILES    64 x 128              3 * (C // 16 or C // 8)  6 of 9      the direct form
+
+The differences between the rows are behaviour, not drift: F(4, 3) produces four outputs a tile, so its pixel tile is twice as wide;
+the one-dimensional routes loop over the three kernel rows (3 * ...) and F(2, 3) takes 16-channel K chunks when C allows it, the
+two-dimensional route has one K tile per 8 channels; only F(2, 3) refuses a split-K launch over an odd number of pixels (its
+epilogue reduces pixel pairs).  The host mirrors wino_wanted / wino2d_wanted / wino43_wanted decide before anything is packed and
+see the channel counts per concat source: wino_wanted counts 16-channel chunks only when EVERY source is a multiple of 16, the launch
+when their sum is -- the library then picks the chunk width (dp_conv_wino_supported).  An F(2x2, 3x3) operand that is refused goes
+to the direct form, not to F(2, 3): the engine packs one operand per layer.
 """
 import ctypes as C
 import os
@@ -347,6 +363,23 @@ class ConvSpec:
         return (tot - self.k) // 2 + 1, (totw - self.k) // 2 + 1
 
 
+def _same3x3(spec, sym_ok=False):
+    """3x3 / stride 1 / pad 1 without upsample, not a `keep` (class kernel) and not a `sym` (general form) spec: the one geometry the
+    Winograd kernels take.  sym_ok: conv_wgrad has always let a general-form 3x3 / 1 / 1 spec through (same geometry)."""
+    return (not getattr(spec, 'keep', False) and (sym_ok or not getattr(spec, 'sym', False)) and spec.kh == 3 and spec.kw == 3
+            and spec.stride == 1 and spec.pad_h == 1 and spec.pad_w == 1 and not spec.ups)
+
+
+def _wino_splits(tiles, n_iter, min_tiles):
+    """The grid rule of every Winograd route: 1 for a grid of at least min_tiles tiles; for a smaller one the split-K count (>= 8 of
+    the n_iter K tiles a slice, like _conv_ksplit does for the direct form) when it is >= 2 and supplies at least half of the wanted
+    workgroups; else 0 = not this route."""
+    if tiles >= min_tiles:
+        return 1
+    ks = min(min_tiles // max(tiles, 1), n_iter // 8)
+    return ks if ks >= 2 and tiles * ks >= min_tiles // 2 else 0
+
+
 # ---- Winograd F(2, 3) along W for the 3x3 / stride 1 / pad 1 convolutions (csrc/winograd.hip): 2/3 of the multiplies ----------
 WINO = os.environ.get('DP_WINO', '1') not in ('0', '')
 WINO_MIN_TILES = int(os.environ.get('DP_WINO_MIN_TILES', '512'))     # 64 x 128-pixel tiles; smaller grids keep the split-K direct form
@@ -356,21 +389,15 @@ def wino_wanted(M, C_sources, N, H, W, spec):
     """Host-side mirror of the kernel's shape rule (wino_bk in csrc/winograd.hip) plus the grid-size rule: True when a 3x3 / stride
     1 / pad 1 convolution with M output rows over N x H x W pixels and the given channel counts per concat source should go to
     dp_conv_wino.  Decided before anything is packed, so layers that never qualify never get a Winograd operand."""
-    if not WINO or getattr(spec, 'keep', False) or getattr(spec, 'sym', False):
-        return False
-    if not (spec.kh == 3 and spec.kw == 3 and spec.stride == 1 and spec.pad_h == 1 and spec.pad_w == 1 and not spec.ups):
+    if not WINO or not _same3x3(spec):
         return False
     if W < 4 or W > 256 or (W & (W - 1)) or ((H * W) & 1):
         return False
     if any(c % 8 for c in C_sources) or M < 16:          # conv_out (3 output rows) is an HBM-bound stencil: conv_few_out_kernel
         return False
-    tiles = -(-M // 64) * -(-(N * H * W) // 128)
-    if tiles >= WINO_MIN_TILES:
-        return True
-    C = sum(C_sources)                                   # smaller grids: split-K must supply >= half of the wanted workgroups
+    C = sum(C_sources)
     n_iter = 3 * (C // 16 if all(c % 16 == 0 for c in C_sources) else C // 8)
-    ks = min(WINO_MIN_TILES // max(tiles, 1), n_iter // 8)
-    return ks >= 2 and tiles * ks >= WINO_MIN_TILES // 2
+    return bool(_wino_splits(-(-M // 64) * -(-(N * H * W) // 128), n_iter, WINO_MIN_TILES))
 
 
 def pack_weight_wino(w, mode):
@@ -400,25 +427,18 @@ WINO2D_MIN_FILL = float(os.environ.get('DP_WINO2D_MIN_FILL', '0.7'))     # M / (
 
 
 def wino2d_wanted(M, C_sources, N, H, W, spec):
-    """Shape rule (wino2d_ok in csrc/winograd2d.hip) + grid rule (_conv_wino2d) + row-tile fill: True when a 3x3 / stride 1 / pad 1
+    """Shape rule (wino2d_ok in csrc/winograd2d.hip) + grid rule (_wino_splits) + row-tile fill: True when a 3x3 / stride 1 / pad 1
     convolution should go to dp_conv_wino2d.  [measured, round 6, profiles/round6_wino2d_gate.txt, batch 256, against F(2, 3):
     128 -> 128 @ 32 x 32 1.43x forward / 1.31x input gradient, 256 -> 256 @ 16 x 16 1.33x / 1.29x, @ 8 x 8 1.21x, @ 4 x 4 1.13x,
     192 -> 192 @ 16 x 16 1.27x, 384 -> 384 @ 32 x 32 (12 latents) 1.24x; 96 -> 96 @ 32 x 32 0.97x: 64-row tiles fill 75 %.  With the
     tuned kernel (profiles/round6_wino2d_tuned.txt): 1.50x / 1.40x, 1.46x / 1.39x, 1.42x, 1.38x, 1.34x, 1.28x, 1.09x / 1.04x.]"""
-    if not WINO or getattr(spec, 'keep', False) or getattr(spec, 'sym', False):
-        return False
-    if not (spec.kh == 3 and spec.kw == 3 and spec.stride == 1 and spec.pad_h == 1 and spec.pad_w == 1 and not spec.ups):
+    if not WINO or not _same3x3(spec):
         return False
     if not wino2d_shape_ok(M, C_sources, N, H, W):
         return False
     if M / float(_wino2d_rows(M)) < WINO2D_MIN_FILL:
         return False
-    tiles = -(-M // 64) * -(-(N * H * W) // 128)
-    if tiles >= WINO2D_MIN_TILES:
-        return True
-    n_iter = sum(C_sources) // 8
-    ks = min(WINO2D_MIN_TILES // max(tiles, 1), n_iter // 8)
-    return ks >= 2 and tiles * ks >= WINO2D_MIN_TILES // 2
+    return bool(_wino_splits(-(-M // 64) * -(-(N * H * W) // 128), sum(C_sources) // 8, WINO2D_MIN_TILES))
 
 
 PACK_BATCH_DERIVED = os.environ.get('DP_PACK_BATCH_DERIVED', '1') != '0'   # upsample class kernels and q | k | v concatenations join the batched packer (engine.prepare_packs)
@@ -438,30 +458,9 @@ def pack_weight_wino2d(w, mode):
 
 
 def _conv_wino2d(p, wino2d, act_bytes):
-    """Run the filled parameter block through dp_conv_wino2d when the kernel takes the shape and the grid is big enough (split-K for
-    small grids, like _conv_wino); False = the caller goes on to F(2, 3) / the direct form."""
-    if not WINO2D:
-        return False
-    U, ld = wino2d
-    tiles = -(-p.M // 64) * -(-p.NPIX // 128)
-    ks = 1
-    if tiles < WINO2D_MIN_TILES:
-        n_iter = p.C // 8
-        ks = min(WINO2D_MIN_TILES // max(tiles, 1), n_iter // 8)
-        if ks < 2 or tiles * ks < WINO2D_MIN_TILES // 2:
-            return False
-    A0, lda0, ab0 = p.A, p.lda, p.a_bytes
-    p.A, p.lda, p.a_bytes = _p(U), ld, U.numel() * 4
-    if ks > 1:
-        ws_t = _workspace(ks * p.M * p.NPIX, U.device)
-        p._keep = (ws_t,)
-        p.ksplit, p.ws, p.tile_counters = ks, _p(ws_t), None
-    if not _lib().dp_conv_wino2d_supported(C.byref(p)):
-        p.A, p.lda, p.a_bytes, p.ksplit, p.ws = A0, lda0, ab0, 1, None
-        return False
-    L.check(_run(lambda: _lib().dp_conv_wino2d(C.byref(p), _stream()), _wino2d_name(p), 2.0 * p.M * p.NPIX * p.C * 4,
-                 act_bytes + 4.0 * U.numel()), 'dp_conv_wino2d')
-    return True
+    """Run the filled parameter block through dp_conv_wino2d when the route takes it (_conv_wino_route); False = the caller goes
+    on to the direct form."""
+    return _conv_wino_route('F(2x2, 3x3)', p, wino2d, act_bytes)
 
 
 def _wino2d_name(p):
@@ -507,18 +506,11 @@ WINO43_MIN_TILES = int(os.environ.get('DP_WINO43_MIN_TILES', '512'))      # 64 x
 def wino43_wanted(M, C_sources, N, H, W, spec):
     """Host-side mirror of wino43_ok (csrc/winograd43.hip) + the grid rule: a no-grad 3x3 / stride 1 / pad 1 convolution that
     should go to dp_conv_wino43."""
-    if not WINO43 or not WINO or getattr(spec, 'keep', False) or getattr(spec, 'sym', False):
-        return False
-    if not (spec.kh == 3 and spec.kw == 3 and spec.stride == 1 and spec.pad_h == 1 and spec.pad_w == 1 and not spec.ups):
+    if not WINO43 or not WINO or not _same3x3(spec):
         return False
     if W < 4 or W > 256 or (W & (W - 1)) or ((H * W) & 3) or any(c % 8 for c in C_sources) or M < 16:
         return False
-    tiles = -(-M // 64) * -(-(N * H * W) // 256)
-    if tiles >= WINO43_MIN_TILES:
-        return True
-    n_iter = 3 * (sum(C_sources) // 8)
-    ks = min(WINO43_MIN_TILES // max(tiles, 1), n_iter // 8)
-    return ks >= 2 and tiles * ks >= WINO43_MIN_TILES // 2
+    return bool(_wino_splits(-(-M // 64) * -(-(N * H * W) // 256), 3 * (sum(C_sources) // 8), WINO43_MIN_TILES))
 
 
 def pack_weight_wino43(w):
@@ -536,61 +528,63 @@ def _wino43_name(p):
 
 
 def _conv_wino43(p, wino43, act_bytes):
-    """Run the filled parameter block through dp_conv_wino43 when the kernel takes the shape and the grid is big enough (split-K
-    for small grids, like _conv_wino); False = the caller goes on to F(2, 3) / the direct form."""
-    if not WINO43:
-        return False
-    U, ld = wino43
-    tiles = -(-p.M // 64) * -(-p.NPIX // 256)
-    ks = 1
-    if tiles < WINO43_MIN_TILES:
-        n_iter = 3 * (p.C // 8)
-        ks = min(WINO43_MIN_TILES // max(tiles, 1), n_iter // 8)
-        if ks < 2 or tiles * ks < WINO43_MIN_TILES // 2:
-            return False
-    A0, lda0, ab0 = p.A, p.lda, p.a_bytes
-    p.A, p.lda, p.a_bytes = _p(U), ld, U.numel() * 4
-    if ks > 1:
-        ws_t = _workspace(ks * p.M * p.NPIX, U.device)
-        p._keep = (ws_t,)
-        p.ksplit, p.ws, p.tile_counters = ks, _p(ws_t), None
-    if not _lib().dp_conv_wino43_supported(C.byref(p)):
-        p.A, p.lda, p.a_bytes, p.ksplit, p.ws = A0, lda0, ab0, 1, None
-        return False
-    L.check(_run(lambda: _lib().dp_conv_wino43(C.byref(p), _stream()), _wino43_name(p), 2.0 * p.M * p.NPIX * p.C * 4.5,
-                 act_bytes + 4.0 * U.numel()), 'dp_conv_wino43')
-    return True
+    """Run the filled parameter block through dp_conv_wino43 when the route takes it (_conv_wino_route); False = the caller goes
+    on to F(2, 3) / F(2x2, 3x3) / the direct form."""
+    return _conv_wino_route('F(4, 3)', p, wino43, act_bytes)
 
 
 def _conv_wino(p, wino, act_bytes):
-    """Run the filled parameter block through dp_conv_wino when the kernel takes the shape and the grid is big enough; False =
-    the caller launches the direct form."""
+    """Run the filled parameter block through dp_conv_wino -- or, for a ('2d', U, ld) operand (engine: wino2d_wanted said yes),
+    dp_conv_wino2d -- when the route takes it (_conv_wino_route); False = the caller launches the direct form."""
     if not WINO:
         return False
-    if wino[0] == '2d':                                # ('2d', U, ld): the F(2x2, 3x3) operand (engine: wino2d_wanted said yes)
+    if isinstance(wino[0], str):                       # ('2d', U, ld)
         return _conv_wino2d(p, wino[1:], act_bytes)
-    U, ld = wino
-    tiles = -(-p.M // 64) * -(-p.NPIX // 128)
-    ks = 1
-    if tiles < WINO_MIN_TILES:
-        # small grids: split the (channel chunk, kernel row) loop like _conv_ksplit does for the direct form (>= 8 K tiles a slice)
-        n_iter = 3 * (p.C // 16 if p.C % 16 == 0 else p.C // 8)
-        ks = min(WINO_MIN_TILES // max(tiles, 1), n_iter // 8)
-        if ks < 2 or tiles * ks < WINO_MIN_TILES // 2 or (p.NPIX & 1):
-            return False
+    return _conv_wino_route('F(2, 3)', p, wino, act_bytes)
+
+
+def _wino_rows(p):
+    """The launcher's tile rule (csrc/winograd.hip): one 32-row block a workgroup for wide images and when it pads fewer rows, else two."""
+    return 1 if (p.g.Wo > 128 or -(-p.M // 32) * 32 < -(-p.M // 64) * 64) else 2
+
+
+# route: (switch, grid threshold [both module constants, read by name at call time], pixels per tile, K tiles of the block, refusal
+# of a split launch or None, shape rule and launch symbols, multiplies per output and channel pair (the direct form: 9), launch name
+# from the block and the answer of the shape rule).  The differences between the rows are intended: see the table in the module docstring.
+_WINO_ROUTES = {
+    'F(2, 3)': ('WINO', 'WINO_MIN_TILES', 128, lambda p: 3 * (p.C // 16 if p.C % 16 == 0 else p.C // 8), lambda p: p.NPIX & 1,
+                'dp_conv_wino_supported', 'dp_conv_wino', 6, lambda p, bk: _wino_name(p, bk, _wino_rows(p))),
+    'F(2x2, 3x3)': ('WINO2D', 'WINO2D_MIN_TILES', 128, lambda p: p.C // 8, None,
+                    'dp_conv_wino2d_supported', 'dp_conv_wino2d', 4, lambda p, ok: _wino2d_name(p)),
+    'F(4, 3)': ('WINO43', 'WINO43_MIN_TILES', 256, lambda p: 3 * (p.C // 8), None,
+                'dp_conv_wino43_supported', 'dp_conv_wino43', 4.5, lambda p, ok: _wino43_name(p)),
+}
+_G = globals()
+
+
+def _conv_wino_route(route, p, operand, act_bytes):
+    """The one launch body of the Winograd routes: grid rule (split-K for small grids), the operand in place of the direct one, the
+    split-K workspace, the library's shape rule -- refused: the block is as it was, False -- and the launch."""
+    switch, min_tiles, pix, n_iter, split_refused, rule, sym, mults, name = _WINO_ROUTES[route]
+    if not _G[switch]:
+        return False
+    U, ld = operand
+    ks = _wino_splits(-(-p.M // 64) * -(-p.NPIX // pix), n_iter(p), _G[min_tiles])
+    if not ks or (ks > 1 and split_refused is not None and split_refused(p)):
+        return False
     A0, lda0, ab0 = p.A, p.lda, p.a_bytes
     p.A, p.lda, p.a_bytes = _p(U), ld, U.numel() * 4
     if ks > 1:
         ws_t = _workspace(ks * p.M * p.NPIX, U.device)
         p._keep = (ws_t,)
         p.ksplit, p.ws, p.tile_counters = ks, _p(ws_t), None
-    bk = _lib().dp_conv_wino_supported(C.byref(p))
-    if not bk:
+    lib = _lib()
+    ok = getattr(lib, rule)(C.byref(p))
+    if not ok:
         p.A, p.lda, p.a_bytes, p.ksplit, p.ws = A0, lda0, ab0, 1, None
         return False
-    wr = 1 if (p.g.Wo > 128 or -(-p.M // 32) * 32 < -(-p.M // 64) * 64) else 2          # the launcher's tile rule (csrc/winograd.hip)
-    L.check(_run(lambda: _lib().dp_conv_wino(C.byref(p), _stream()), _wino_name(p, bk, wr), 2.0 * p.M * p.NPIX * p.C * 6,
-                 act_bytes + 4.0 * U.numel()), 'dp_conv_wino')
+    L.check(_run(lambda: getattr(lib, sym)(C.byref(p), _stream()), name(p, ok), 2.0 * p.M * p.NPIX * p.C * mults,
+                 act_bytes + 4.0 * U.numel()), sym)
     return True
 
 
@@ -600,6 +594,37 @@ def _wino_name(p, bk, wr):
 
 def _wgrad_wino_name(p, bt):
     return 'wgrad_wino_kernel<%d, %d>' % ((3, 3) if bt == 96 else (2, 2))
+
+
+def _conv_gemm_params(A, lda, x, x2, geom, M, K, NPIX, ntaps, out, o_img_stride, *, alpha=1.0, post_scale=1.0, accumulate=False,
+                      a_kc=0, batch=None):
+    """The dp_conv_gemm_params block of out[M, NPIX] = A (x) gathered(cat(x, x2)) over K channels and ntaps taps, tile chosen.
+    batch = (Z, a_bs, x_bs, o_bs): Z independent matrix products (bmm_tn / bmm_nn) -- operand extents from the matrix shapes, nothing
+    read in front of x (one tap, no padding), no 96-row preference."""
+    p = L.ConvGemmParams()
+    Z, a_bs, x_bs, o_bs = batch or (1, 0, 0, 0)
+    p.A, p.a_bs, p.lda, p.a_kc = _p(A), a_bs, lda, a_kc
+    p.X1, p.X2, p.x_bs = _p(x), _p(x2), x_bs
+    if batch is None:
+        p.x_guard = 1 if (_guarded(x) and _guarded(x2)) else 0
+        p.a_bytes, p.x1_bytes, p.x2_bytes = A.numel() * 4, _extent_bytes(x), _extent_bytes(x2)
+    else:
+        p.x_guard = 1
+        p.a_bytes, p.x1_bytes, p.x2_bytes = M * K * 4, K * NPIX * 4, 0
+    p.g = geom
+    p.M, p.C, p.NPIX, p.ntaps, p.batches = M, K, NPIX, ntaps, Z
+    p.tile = pick_tile(M, NPIX, Z)
+    if batch is None:
+        _prefer_tile96(p)
+    p.out, p.o_img_stride, p.o_bs = _p(out), o_img_stride, o_bs
+    p.alpha, p.post_scale, p.accumulate = alpha, post_scale, 1 if accumulate else 0
+    return p
+
+
+def _conv_gemm_launch(p, device, abytes, label):
+    """The direct form: split-K choice, then dp_conv_gemm."""
+    _conv_ksplit(p, device)
+    L.check(_run(lambda: _lib().dp_conv_gemm(C.byref(p), _stream()), _cg_name(p), 2.0 * p.M * p.NPIX * p.C * p.ntaps, abytes), label)
 
 
 def conv_forward(x, x2, wp, ld, Cout, spec, *, bias=None, tadd=None, res=None, post_scale=1.0, alpha=1.0, out=None,
@@ -621,32 +646,22 @@ def conv_forward(x, x2, wp, ld, Cout, spec, *, bias=None, tadd=None, res=None, p
         out = empty_act((N, Cout, Ho, Wo), x.device)
     so = _chk_act(out)
     assert out.shape == (N, Cout, Ho, Wo)
-    p = L.ConvGemmParams()
-    p.A, p.a_bs, p.lda, p.a_kc = _p(wp), 0, ld, 0
-    p.X1, p.X2, p.x_bs = _p(x), _p(x2), 0
-    p.x_guard = 1 if (_guarded(x) and _guarded(x2)) else 0
-    p.a_bytes, p.x1_bytes, p.x2_bytes = wp.numel() * 4, _extent_bytes(x), _extent_bytes(x2)
-    p.g = _geom(Ho, Wo, Hs, Ws, Hs << spec.ups, Ws << spec.ups, spec.kw, spec.stride, 1, spec.pad_h, spec.pad_w, spec.ups,
-                C1 if x2 is not None else Cin, s1, s2)
-    p.M, p.C, p.NPIX, p.ntaps, p.batches = Cout, Cin, N * Ho * Wo, spec.kh * spec.kw, 1
+    geom = _geom(Ho, Wo, Hs, Ws, Hs << spec.ups, Ws << spec.ups, spec.kw, spec.stride, 1, spec.pad_h, spec.pad_w, spec.ups,
+                 C1 if x2 is not None else Cin, s1, s2)
+    p = _conv_gemm_params(wp, ld, x, x2, geom, Cout, Cin, N * Ho * Wo, spec.kh * spec.kw, out, so, alpha=alpha, post_scale=post_scale,
+                          accumulate=accumulate)
     p.act = 1 if relu else 0
-    p.tile = pick_tile(Cout, N * Ho * Wo)
-    _prefer_tile96(p)
-    p.out, p.o_img_stride, p.o_bs = _p(out), so, 0
-    p.alpha, p.post_scale = alpha, post_scale
     p.bias = _p(bias)
     p.tadd, p.tadd_stride = _p(tadd), (tadd.stride(0) if tadd is not None else 0)
     if res is not None:
         p.res, p.r_img_stride = _p(res), _chk_act(res)
         assert res.shape == out.shape
-    p.accumulate = 1 if accumulate else 0
-    if wino43 is not None and _conv_wino43(p, wino43, 4.0 * (N * Cin * Hs * Ws + out.numel())):
+    act_bytes = 4.0 * (N * Cin * Hs * Ws + out.numel())
+    if wino43 is not None and _conv_wino43(p, wino43, act_bytes):
         return out
-    if wino is not None and _conv_wino(p, wino, 4.0 * (N * Cin * Hs * Ws + out.numel())):
+    if wino is not None and _conv_wino(p, wino, act_bytes):
         return out
-    _conv_ksplit(p, x.device)
-    L.check(_run(lambda: _lib().dp_conv_gemm(C.byref(p), _stream()), _cg_name(p), 2.0 * p.M * p.NPIX * p.C * p.ntaps,
-                 4.0 * (N * Cin * Hs * Ws + wp.numel() + out.numel())), 'dp_conv_gemm(forward)')
+    _conv_gemm_launch(p, x.device, 4.0 * (N * Cin * Hs * Ws + wp.numel() + out.numel()), 'dp_conv_gemm(forward)')
     return out
 
 
@@ -660,24 +675,12 @@ def conv_dgrad(dy, wd, ldd, Cin, spec, in_hw, *, alpha=1.0, out=None, accumulate
         out = empty_act((N, Cin, Hv, Wv), dy.device)
     so = _chk_act(out)
     assert out.shape == (N, Cin, Hv, Wv)
-    p = L.ConvGemmParams()
-    p.A, p.a_bs, p.lda, p.a_kc = _p(wd), 0, ldd, 0
-    p.X1, p.X2, p.x_bs = _p(dy), None, 0
-    p.x_guard = 1 if _guarded(dy) else 0
-    p.a_bytes, p.x1_bytes, p.x2_bytes = wd.numel() * 4, _extent_bytes(dy), 0
     # dX[h] = sum_ky' dY[(h + ky' - (k-1-pad)) / stride] Wflip[ky']
-    p.g = _geom(Hv, Wv, Ho, Wo, Ho, Wo, spec.kw, 1, spec.stride, spec.kh - 1 - spec.pad_h, spec.kw - 1 - spec.pad_w, 0, Cout, sd, 0)
-    p.M, p.C, p.NPIX, p.ntaps, p.batches = Cin, Cout, N * Hv * Wv, spec.kh * spec.kw, 1
-    p.tile = pick_tile(Cin, N * Hv * Wv)
-    _prefer_tile96(p)
-    p.out, p.o_img_stride, p.o_bs = _p(out), so, 0
-    p.alpha, p.post_scale = alpha, 1.0
-    p.accumulate = 1 if accumulate else 0
+    geom = _geom(Hv, Wv, Ho, Wo, Ho, Wo, spec.kw, 1, spec.stride, spec.kh - 1 - spec.pad_h, spec.kw - 1 - spec.pad_w, 0, Cout, sd, 0)
+    p = _conv_gemm_params(wd, ldd, dy, None, geom, Cin, Cout, N * Hv * Wv, spec.kh * spec.kw, out, so, alpha=alpha, accumulate=accumulate)
     if wino is not None and _conv_wino(p, wino, 4.0 * (dy.numel() + out.numel())):
         return out
-    _conv_ksplit(p, dy.device)
-    L.check(_run(lambda: _lib().dp_conv_gemm(C.byref(p), _stream()), _cg_name(p), 2.0 * p.M * p.NPIX * p.C * p.ntaps,
-                 4.0 * (dy.numel() + wd.numel() + out.numel())), 'dp_conv_gemm(dgrad)')
+    _conv_gemm_launch(p, dy.device, 4.0 * (dy.numel() + wd.numel() + out.numel()), 'dp_conv_gemm(dgrad)')
     return out
 
 
@@ -716,20 +719,9 @@ def conv_dgrad_s2(dy, packs, Cin, spec, in_hw, add=None):
             tw, pad_w = _s2_taps(pw, spec.pad)
             wd, ldd = packs[2 * ph + pw]
             out = q[2 * ph + pw]
-            p = L.ConvGemmParams()
-            p.A, p.a_bs, p.lda, p.a_kc = _p(wd), 0, ldd, 0
-            p.X1, p.X2, p.x_bs = _p(dy), None, 0
-            p.x_guard = 1 if _guarded(dy) else 0
-            p.a_bytes, p.x1_bytes, p.x2_bytes = wd.numel() * 4, _extent_bytes(dy), 0
-            p.g = _geom(Ho, Wo, Ho, Wo, Ho, Wo, len(tw), 1, 1, pad_h, pad_w, 0, Cout, sd, 0)
-            p.M, p.C, p.NPIX, p.ntaps, p.batches = Cin, Cout, N * Ho * Wo, len(th) * len(tw), 1
-            p.tile = pick_tile(Cin, N * Ho * Wo)
-            _prefer_tile96(p)
-            p.out, p.o_img_stride, p.o_bs = _p(out), Cin * Ho * Wo, 0
-            p.alpha, p.post_scale = 1.0, 1.0
-            _conv_ksplit(p, dy.device)
-            L.check(_run(lambda: _lib().dp_conv_gemm(C.byref(p), _stream()), _cg_name(p), 2.0 * p.M * p.NPIX * p.C * p.ntaps,
-                         4.0 * (dy.numel() + wd.numel() + out.numel())), 'dp_conv_gemm(dgrad, stride-2 parity class)')
+            geom = _geom(Ho, Wo, Ho, Wo, Ho, Wo, len(tw), 1, 1, pad_h, pad_w, 0, Cout, sd, 0)
+            p = _conv_gemm_params(wd, ldd, dy, None, geom, Cin, Cout, N * Ho * Wo, len(th) * len(tw), out, Cin * Ho * Wo)
+            _conv_gemm_launch(p, dy.device, 4.0 * (dy.numel() + wd.numel() + out.numel()), 'dp_conv_gemm(dgrad, stride-2 parity class)')
     return interleave2x2(q, add)
 
 
@@ -904,6 +896,48 @@ WGRAD_WINO2D_BLOCKS = int(os.environ.get('DP_WGRAD_WINO2D_BLOCKS', '512'))
 WGRAD_WINO2D_MIN_FILL = float(os.environ.get('DP_WGRAD_WINO2D_MIN_FILL', '0.7'))     # Cout x Cin against its 64 x 32 tiles
 
 
+def _nt_gemm_params(A, a_img_stride, x, x2, geom, M, Cc, ncols, ntaps, P, splits, pps, tile, alpha, ldo, batch=None):
+    """The dp_nt_gemm_params block of a weight gradient: rows from A [N, M, Ho, Wo], columns gathered from cat(x, x2), P pixels in
+    `splits` slices of pps.  batch = (Z, a_bs, x_bs, batched): plain [M, P] x [ncols, P] matrices (bmm_nt, linear_forward) -- operand
+    extents from the matrix shapes."""
+    p = L.NtGemmParams()
+    Z, a_bs, x_bs, batched = batch or (1, 0, 0, 0)
+    p.A, p.a_bs, p.a_img_stride = _p(A), a_bs, a_img_stride
+    p.X1, p.X2, p.x_bs = _p(x), _p(x2), x_bs
+    if batch is None:
+        p.a_bytes, p.x1_bytes, p.x2_bytes = _extent_bytes(A), _extent_bytes(x), _extent_bytes(x2)
+    else:
+        p.a_bytes, p.x1_bytes, p.x2_bytes = M * P * 4, ncols * P * 4, 0
+    p.g = geom
+    p.M, p.C, p.NCOLS, p.ntaps, p.P = M, Cc, ncols, ntaps, P
+    p.batches, p.splits, p.p_per_split, p.tile, p.batched = Z, splits, pps, tile, batched
+    p.alpha, p.ldo = alpha, ldo
+    return p
+
+
+def _wgrad_launch(p, gw, accumulate, sym, name, flops, label, taps, device):
+    """The tail of every weight gradient: one slice writes (accumulates into) gw; several write partials to the workspace -- with
+    `taps` tap-major, [split][tap][M][C]: 32 lanes store 128 contiguous bytes (the torch layout would scatter 4-byte stores 4 * taps
+    bytes apart: ~2.3x write amplification measured with WRITE_SIZE) -- which dp_splitk_reduce_taps (taps) / dp_splitk_reduce (taps =
+    0: merged taps, gw's own layout) adds up in a fixed order."""
+    acc = 1 if accumulate else 0
+    if p.splits == 1:
+        p.out, p.o_bs, p.accumulate = _p(gw), 0, acc
+        L.check(_run(lambda: getattr(_lib(), sym)(C.byref(p), _stream()), name, flops), label)
+        return gw
+    n = gw.numel()
+    ws = _workspace(p.splits * n, device)
+    p.out, p.o_bs, p.accumulate = _p(ws), n, 0
+    if taps:
+        p.ldo, p.o_col_stride, p.o_tap_stride = p.C, 1, p.M * p.C
+    L.check(_run(lambda: getattr(_lib(), sym)(C.byref(p), _stream()), name, flops), label)
+    if taps:
+        L.check(_lib().dp_splitk_reduce_taps(_p(ws), n, p.splits, _p(gw), p.M * p.C, taps, acc, _stream()), 'dp_splitk_reduce_taps')
+    else:
+        L.check(_lib().dp_splitk_reduce(_p(ws), n, p.splits, _p(gw), n, acc, _stream()), 'dp_splitk_reduce')
+    return gw
+
+
 def _conv_wgrad_wino2d(dy, x, x2, gw, spec, alpha, accumulate, sd, s1, s2):
     """3x3 / stride 1 / pad 1 weight gradient on the two-dimensional transposed Winograd F(3x3, 2x2) kernel (csrc/wgrad2d.hip): 4/9 of the
     direct multiplies, 2/3 of _conv_wgrad_wino's.  Same tap-major split-K partials and reduction launch.  None = the kernel does not
@@ -914,36 +948,17 @@ def _conv_wgrad_wino2d(dy, x, x2, gw, spec, alpha, accumulate, sd, s1, s2):
     P = N * Ho * Wo
     if Wo not in (8, 16, 32) or (Ho & 1) or ((Ho * Wo) & (Ho * Wo - 1)) or Ho * Wo < 64 or (x2 is not None and C1 % 32):
         return None
-    p = L.NtGemmParams()
-    p.A, p.a_bs, p.a_img_stride = _p(dy), 0, sd
-    p.X1, p.X2, p.x_bs = _p(x), _p(x2), 0
-    p.a_bytes, p.x1_bytes, p.x2_bytes = _extent_bytes(dy), _extent_bytes(x), _extent_bytes(x2)
-    p.g = _geom(Ho, Wo, Ho, Wo, Ho, Wo, 3, 1, 1, 1, 1, 0, C1 if x2 is not None else Cin, s1, s2)
-    p.M, p.C, p.NCOLS, p.ntaps, p.P = Cout, Cin, Cin, 9, P
     tiles = -(-Cout // 64) * (-(-C1 // 32) + (-(-(Cin - C1) // 32) if x2 is not None else 0))
     nt = P // 64                                       # K tiles of 16 tiles = 64 pixels
     splits = max(1, min(WGRAD_WINO2D_BLOCKS // tiles, nt // 4))
     tps = -(-nt // splits)
     splits = -(-nt // tps)
-    p.batches, p.splits, p.p_per_split, p.tile, p.batched = 1, splits, tps * 64, 0, 0
-    p.alpha = alpha
-    p.ldo = Cin * 9
+    geom = _geom(Ho, Wo, Ho, Wo, Ho, Wo, 3, 1, 1, 1, 1, 0, C1 if x2 is not None else Cin, s1, s2)
+    p = _nt_gemm_params(dy, sd, x, x2, geom, Cout, Cin, Cin, 9, P, splits, tps * 64, 0, alpha, Cin * 9)
     if not _lib().dp_wgrad_wino2d_supported(C.byref(p)):
         return None
-    flops = 2.0 * Cout * Cin * 4 * P
     name = ('wgrad_wino2d_tail_kernel<%d>' if _wino2d_tail(Cout) else 'wgrad_wino2d_kernel<%d>') % {8: 3, 16: 4, 32: 5}[Wo]
-    if splits == 1:
-        p.out, p.o_bs, p.accumulate = _p(gw), 0, 1 if accumulate else 0
-        L.check(_run(lambda: _lib().dp_wgrad_wino2d(C.byref(p), _stream()), name, flops), 'dp_wgrad_wino2d')
-    else:
-        n = Cout * Cin * 9
-        ws = _workspace(splits * n, dy.device)
-        p.out, p.o_bs, p.accumulate = _p(ws), n, 0
-        p.ldo, p.o_col_stride, p.o_tap_stride = Cin, 1, Cout * Cin          # tap-major partials [split][tap][Cout][Cin]
-        L.check(_run(lambda: _lib().dp_wgrad_wino2d(C.byref(p), _stream()), name, flops), 'dp_wgrad_wino2d')
-        L.check(_lib().dp_splitk_reduce_taps(_p(ws), n, splits, _p(gw), Cout * Cin, 9, 1 if accumulate else 0, _stream()),
-                'dp_splitk_reduce_taps')
-    return gw
+    return _wgrad_launch(p, gw, accumulate, 'dp_wgrad_wino2d', name, 2.0 * Cout * Cin * 4 * P, 'dp_wgrad_wino2d', 9, dy.device)
 
 
 def _conv_wgrad_wino(dy, x, x2, gw, spec, alpha, accumulate, sd, s1, s2):
@@ -953,12 +968,6 @@ def _conv_wgrad_wino(dy, x, x2, gw, spec, alpha, accumulate, sd, s1, s2):
     C1 = x.shape[1]
     Cin = C1 + (x2.shape[1] if x2 is not None else 0)
     P = N * Ho * Wo
-    p = L.NtGemmParams()
-    p.A, p.a_bs, p.a_img_stride = _p(dy), 0, sd
-    p.X1, p.X2, p.x_bs = _p(x), _p(x2), 0
-    p.a_bytes, p.x1_bytes, p.x2_bytes = _extent_bytes(dy), _extent_bytes(x), _extent_bytes(x2)
-    p.g = _geom(Ho, Wo, Ho, Wo, Ho, Wo, 3, 1, 1, 1, 1, 0, C1 if x2 is not None else Cin, s1, s2)
-    p.M, p.C, p.NCOLS, p.ntaps, p.P = Cout, Cin, Cin, 9, P
     # 96 x 96 tiles (nine wavefronts) when they cover [Cout x Cin] with clearly less padding than 64 x 64 tiles
     a64 = (-(-Cout // 64) * 64) * (-(-Cin // 64) * 64)
     a96 = (-(-Cout // 96) * 96) * (-(-Cin // 96) * 96)
@@ -968,25 +977,13 @@ def _conv_wgrad_wino(dy, x, x2, gw, spec, alpha, accumulate, sd, s1, s2):
     splits = max(1, min(WGRAD_BLOCKS // tiles, nt // 4))
     tps = -(-nt // splits)
     splits = -(-nt // tps)
-    p.batches, p.splits, p.p_per_split, p.tile, p.batched = 1, splits, tps * 32, (3 if bt == 96 else 0), 0
-    p.alpha = alpha
-    p.ldo = Cin * 9
+    geom = _geom(Ho, Wo, Ho, Wo, Ho, Wo, 3, 1, 1, 1, 1, 0, C1 if x2 is not None else Cin, s1, s2)
+    p = _nt_gemm_params(dy, sd, x, x2, geom, Cout, Cin, Cin, 9, P, splits, tps * 32, 3 if bt == 96 else 0, alpha, Cin * 9)
     p.xcd = 0 if os.environ.get('DP_NO_XCD') else 1
     if not _lib().dp_wgrad_wino_supported(C.byref(p)):
         return None
-    flops = 2.0 * Cout * Cin * 6 * P
-    if splits == 1:
-        p.out, p.o_bs, p.accumulate = _p(gw), 0, 1 if accumulate else 0
-        L.check(_run(lambda: _lib().dp_wgrad_wino(C.byref(p), _stream()), _wgrad_wino_name(p, bt), flops), 'dp_wgrad_wino')
-    else:
-        n = Cout * Cin * 9
-        ws = _workspace(splits * n, dy.device)
-        p.out, p.o_bs, p.accumulate = _p(ws), n, 0
-        p.ldo, p.o_col_stride, p.o_tap_stride = Cin, 1, Cout * Cin          # tap-major partials [split][tap][Cout][Cin]
-        L.check(_run(lambda: _lib().dp_wgrad_wino(C.byref(p), _stream()), _wgrad_wino_name(p, bt), flops), 'dp_wgrad_wino')
-        L.check(_lib().dp_splitk_reduce_taps(_p(ws), n, splits, _p(gw), Cout * Cin, 9, 1 if accumulate else 0, _stream()),
-                'dp_splitk_reduce_taps')
-    return gw
+    return _wgrad_launch(p, gw, accumulate, 'dp_wgrad_wino', _wgrad_wino_name(p, bt), 2.0 * Cout * Cin * 6 * P, 'dp_wgrad_wino', 9,
+                         dy.device)
 
 
 def conv_wgrad(dy, x, x2, gw, spec, *, alpha=1.0, accumulate=True, max_splits=None):
@@ -1010,7 +1007,7 @@ def conv_wgrad(dy, x, x2, gw, spec, *, alpha=1.0, accumulate=True, max_splits=No
                and 2 * spec.pad == spec.k - 1)
     if WGRAD_MERGE_TAPS and square and (few_in or few_out):
         return _conv_wgrad_merged(dy, x, gw, spec, alpha, accumulate, few_in)
-    if (WINO and WGRAD_WINO and taps == 9 and square and spec.stride == 1 and spec.pad == 1 and not spec.ups and max_splits is None
+    if (WINO and WGRAD_WINO and _same3x3(spec, sym_ok=True) and max_splits is None
             and (Hs, Ws) == (Ho, Wo) and P % 32 == 0 and -(-Cout // 64) * -(-Cin // 64) * 3 * (P // 1024) >= WGRAD_WINO_MIN_WORK
             # 64 x 64 tiles (or 96 x 96 for the 96-multiples of pruned models): a 96 x 96 gradient fills 56 % of four 64 x 64 tiles and
             # is then slower than the direct kernel's 96 x 96 tile [measured 0.90x]
@@ -1045,30 +1042,10 @@ def conv_wgrad(dy, x, x2, gw, spec, *, alpha=1.0, accumulate=True, max_splits=No
     pps = -(-P // splits)
     pps = (pps + 31) & ~31
     splits = -(-P // pps)
-    p = L.NtGemmParams()
-    p.A, p.a_bs, p.a_img_stride = _p(dy), 0, sd
-    p.X1, p.X2, p.x_bs = _p(x), _p(x2), 0
-    p.a_bytes, p.x1_bytes, p.x2_bytes = _extent_bytes(dy), _extent_bytes(x), _extent_bytes(x2)
-    p.g = geom
-    p.M, p.C, p.NCOLS, p.ntaps, p.P = Cout, Cin, Cin, taps, P
-    p.batches, p.splits, p.p_per_split, p.tile, p.batched = 1, splits, pps, tile, 0
-    p.alpha = alpha
-    p.ldo = ncols
+    p = _nt_gemm_params(dy, sd, x, x2, geom, Cout, Cin, Cin, taps, P, splits, pps, tile, alpha, ncols)
     p.xcd = 0 if os.environ.get('DP_NO_XCD') else 1
-    if splits == 1:
-        p.out, p.o_bs, p.accumulate = _p(gw), 0, 1 if accumulate else 0
-        L.check(_run(lambda: _lib().dp_nt_gemm(C.byref(p), _stream()), _nt_name(p), 2.0 * p.M * p.NCOLS * p.ntaps * p.P), 'dp_nt_gemm(wgrad)')
-    else:
-        n = Cout * ncols
-        ws = _workspace(splits * n, dy.device)
-        p.out, p.o_bs, p.accumulate = _p(ws), n, 0
-        # partials tap-major [split][tap][Cout][Cin]: 32 lanes store 128 contiguous bytes (the torch layout would
-        # scatter 4-byte stores 4*taps bytes apart: ~2.3x write amplification measured with WRITE_SIZE)
-        p.ldo, p.o_col_stride, p.o_tap_stride = Cin, 1, Cout * Cin
-        L.check(_run(lambda: _lib().dp_nt_gemm(C.byref(p), _stream()), _nt_name(p), 2.0 * p.M * p.NCOLS * p.ntaps * p.P), 'dp_nt_gemm(wgrad)')
-        L.check(_lib().dp_splitk_reduce_taps(_p(ws), n, splits, _p(gw), Cout * Cin, taps, 1 if accumulate else 0, _stream()),
-                'dp_splitk_reduce_taps')
-    return gw
+    return _wgrad_launch(p, gw, accumulate, 'dp_nt_gemm', _nt_name(p), 2.0 * p.M * p.NCOLS * p.ntaps * p.P, 'dp_nt_gemm(wgrad)', taps,
+                         dy.device)
 
 
 WGRAD_MERGE_TAPS = True
@@ -1082,38 +1059,23 @@ def _conv_wgrad_merged(dy, x, gw, spec, alpha, accumulate, few_in):
     _, Cin, Hs, Ws = x.shape
     taps = spec.k * spec.k
     P = N * Ho * Wo
-    p = L.NtGemmParams()
     if few_in:
         rows, gat, M, Cg = dy, x, Cout, Cin
-        p.g = _geom(Ho, Wo, Hs, Ws, Hs << spec.ups, Ws << spec.ups, spec.k, spec.stride, 1, spec.pad, spec.pad, spec.ups,
-                    Cin, _chk_act(x), 0)
-        p.ldo, p.ocs, p.merge = Cin * taps, taps, 1
+        geom = _geom(Ho, Wo, Hs, Ws, Hs << spec.ups, Ws << spec.ups, spec.k, spec.stride, 1, spec.pad, spec.pad, spec.ups,
+                     Cin, _chk_act(x), 0)
+        ldo, ocs, merge = Cin * taps, taps, 1
     else:
         rows, gat, M, Cg = x, dy, Cin, Cout
-        p.g = _geom(Hs, Ws, Ho, Wo, Ho, Wo, spec.k, 1, 1, spec.pad, spec.pad, 0, Cout, _chk_act(dy), 0)
-        p.ldo, p.ocs, p.merge = taps, Cin * taps, 3
+        geom = _geom(Hs, Ws, Ho, Wo, Ho, Wo, spec.k, 1, 1, spec.pad, spec.pad, 0, Cout, _chk_act(dy), 0)
+        ldo, ocs, merge = taps, Cin * taps, 3
     tiles = -(-M // 64) * -(-(Cg * taps) // 64)
     splits = max(1, min(WGRAD_BLOCKS // tiles, P // WGRAD_MIN_PIX if P >= 2 * WGRAD_MIN_PIX else 1))
     pps = (-(-P // splits) + 31) & ~31
     splits = -(-P // pps)
-    p.A, p.a_bs, p.a_img_stride = _p(rows), 0, _chk_act(rows)
-    p.X1, p.X2, p.x_bs = _p(gat), None, 0
-    p.a_bytes, p.x1_bytes, p.x2_bytes = _extent_bytes(rows), _extent_bytes(gat), 0
-    p.M, p.C, p.NCOLS, p.ntaps, p.P = M, Cg, Cg * taps, taps, P
-    p.batches, p.splits, p.p_per_split, p.tile, p.batched = 1, splits, pps, 2, 0
-    p.alpha = alpha
-    n = gw.numel()
-    flops = 2.0 * Cout * Cin * taps * P
-    if splits == 1:
-        p.out, p.o_bs, p.accumulate = _p(gw), 0, 1 if accumulate else 0
-        L.check(_run(lambda: _lib().dp_nt_gemm(C.byref(p), _stream()), _nt_name(p), flops), 'dp_nt_gemm(wgrad, merged taps)')
-    else:
-        ws = _workspace(splits * n, dy.device)
-        p.out, p.o_bs, p.accumulate = _p(ws), n, 0
-        L.check(_run(lambda: _lib().dp_nt_gemm(C.byref(p), _stream()), _nt_name(p), flops), 'dp_nt_gemm(wgrad, merged taps)')
-        L.check(_lib().dp_splitk_reduce(_p(ws), n, splits, _p(gw), n, 1 if accumulate else 0, _stream()),
-                'dp_splitk_reduce')
-    return gw
+    p = _nt_gemm_params(rows, _chk_act(rows), gat, None, geom, M, Cg, Cg * taps, taps, P, splits, pps, 2, alpha, ldo)
+    p.ocs, p.merge = ocs, merge
+    return _wgrad_launch(p, gw, accumulate, 'dp_nt_gemm', _nt_name(p), 2.0 * Cout * Cin * taps * P, 'dp_nt_gemm(wgrad, merged taps)', 0,
+                         dy.device)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1129,6 +1091,16 @@ def _bs(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2]
 
 
+def _bmm_conv_gemm(a, lda, a_kc, b, out, Z, M, K, Nn, alpha, accumulate, label):
+    """out[z] = alpha * A[z] b[z] on dp_conv_gemm (one tap): a[z] is A^T with leading dimension lda (a_kc = 0, m-contiguous) or A
+    itself (a_kc = 1, k-contiguous); a single product may split K."""
+    p = _conv_gemm_params(a, lda, b, None, _bgeom(Nn, K), M, K, Nn, 1, out, 0, alpha=alpha, accumulate=accumulate, a_kc=a_kc,
+                          batch=(Z, _bs(a), _bs(b), _bs(out)))
+    if Z == 1:
+        _conv_ksplit(p, a.device)
+    L.check(_run(lambda: _lib().dp_conv_gemm(C.byref(p), _stream()), _cg_name(p), 2.0 * Z * M * Nn * K), label)
+
+
 def bmm_tn(a, b, alpha=1.0, out=None, accumulate=False):
     """out[z, m, n] = alpha * sum_k a[z, k, m] * b[z, k, n]      (QK^T: a=Q, b=K;  dP: a=dO, b=V)"""
     Z, K, M = a.shape
@@ -1137,19 +1109,7 @@ def bmm_tn(a, b, alpha=1.0, out=None, accumulate=False):
     if out is None:
         assert not accumulate
         out = torch.empty((Z, M, Nn), dtype=_f32, device=a.device)
-    p = L.ConvGemmParams()
-    p.A, p.a_bs, p.lda, p.a_kc = _p(a), _bs(a), M, 0
-    p.X1, p.X2, p.x_bs = _p(b), None, _bs(b)
-    p.x_guard = 1                                    # one tap, no padding: nothing is read in front of b
-    p.a_bytes, p.x1_bytes, p.x2_bytes = K * M * 4, K * Nn * 4, 0
-    p.g = _bgeom(Nn, K)
-    p.M, p.C, p.NPIX, p.ntaps, p.batches = M, K, Nn, 1, Z
-    p.tile = pick_tile(M, Nn, Z)
-    p.out, p.o_img_stride, p.o_bs = _p(out), 0, _bs(out)
-    p.alpha, p.post_scale, p.accumulate = alpha, 1.0, 1 if accumulate else 0
-    if Z == 1:
-        _conv_ksplit(p, a.device)
-    L.check(_run(lambda: _lib().dp_conv_gemm(C.byref(p), _stream()), _cg_name(p), 2.0 * Z * M * Nn * K), 'dp_conv_gemm(bmm_tn)')
+    _bmm_conv_gemm(a, M, 0, b, out, Z, M, K, Nn, alpha, accumulate, 'dp_conv_gemm(bmm_tn)')
     return out
 
 
@@ -1161,19 +1121,7 @@ def bmm_nn(a, b, alpha=1.0, out=None, accumulate=False):
     if out is None:
         assert not accumulate
         out = torch.empty((Z, M, Nn), dtype=_f32, device=a.device)
-    p = L.ConvGemmParams()
-    p.A, p.a_bs, p.lda, p.a_kc = _p(a), _bs(a), K, 1
-    p.X1, p.X2, p.x_bs = _p(b), None, _bs(b)
-    p.x_guard = 1
-    p.a_bytes, p.x1_bytes, p.x2_bytes = M * K * 4, K * Nn * 4, 0
-    p.g = _bgeom(Nn, K)
-    p.M, p.C, p.NPIX, p.ntaps, p.batches = M, K, Nn, 1, Z
-    p.tile = pick_tile(M, Nn, Z)
-    p.out, p.o_img_stride, p.o_bs = _p(out), 0, _bs(out)
-    p.alpha, p.post_scale, p.accumulate = alpha, 1.0, 1 if accumulate else 0
-    if Z == 1:
-        _conv_ksplit(p, a.device)
-    L.check(_run(lambda: _lib().dp_conv_gemm(C.byref(p), _stream()), _cg_name(p), 2.0 * Z * M * Nn * K), 'dp_conv_gemm(bmm_nn)')
+    _bmm_conv_gemm(a, K, 1, b, out, Z, M, K, Nn, alpha, accumulate, 'dp_conv_gemm(bmm_nn)')
     return out
 
 
@@ -1184,16 +1132,8 @@ def bmm_nt(a, b, alpha=1.0, out=None, col_bias=None):
     assert K2 == K
     if out is None:
         out = torch.empty((Z, M, Nn), dtype=_f32, device=a.device)
-    p = L.NtGemmParams()
-    p.A, p.a_bs, p.a_img_stride = _p(a), _bs(a), 0
-    p.X1, p.X2, p.x_bs = _p(b), None, _bs(b)
-    p.a_bytes, p.x1_bytes, p.x2_bytes = M * K * 4, Nn * K * 4, 0
-    p.g = _bgeom(K, Nn)
-    p.M, p.C, p.NCOLS, p.ntaps, p.P = M, Nn, Nn, 1, K
-    p.batches, p.splits, p.p_per_split, p.batched = Z, 1, 0, 1
-    p.tile = pick_tile(M, Nn, Z)
-    p.out, p.o_bs, p.ldo, p.accumulate = _p(out), _bs(out), Nn, 0
-    p.alpha, p.col_bias = alpha, _p(col_bias)
+    p = _nt_gemm_params(a, 0, b, None, _bgeom(K, Nn), M, Nn, Nn, 1, K, 1, 0, pick_tile(M, Nn, Z), alpha, Nn, batch=(Z, _bs(a), _bs(b), 1))
+    p.out, p.o_bs, p.accumulate, p.col_bias = _p(out), _bs(out), 0, _p(col_bias)
     L.check(_run(lambda: _lib().dp_nt_gemm(C.byref(p), _stream()), _nt_name(p), 2.0 * Z * M * Nn * K), 'dp_nt_gemm(bmm_nt)')
     return out
 
@@ -1216,14 +1156,8 @@ def linear_forward(x, w, bias=None):
     out = torch.empty((N, Co), dtype=_f32, device=x.device)
     pps = (-(-K // splits) + 31) & ~31
     splits = -(-K // pps)
-    p = L.NtGemmParams()
-    p.A, p.a_bs, p.a_img_stride = _p(x), 0, 0
-    p.X1, p.X2, p.x_bs = _p(w), None, 0
-    p.a_bytes, p.x1_bytes, p.x2_bytes = N * K * 4, Co * K * 4, 0
-    p.g = _bgeom(K, Co)
-    p.M, p.C, p.NCOLS, p.ntaps, p.P = N, Co, Co, 1, K
-    p.batches, p.splits, p.p_per_split, p.tile, p.batched = 1, splits, pps, tile, 0
-    p.alpha, p.col_bias, p.ldo = 1.0, _p(bias), Co
+    p = _nt_gemm_params(x, 0, w, None, _bgeom(K, Co), N, Co, Co, 1, K, splits, pps, tile, 1.0, Co, batch=(1, 0, 0, 0))
+    p.col_bias = _p(bias)
     ws = _workspace(splits * N * Co, x.device)
     p.out, p.o_bs, p.accumulate = _p(ws), N * Co, 0
     L.check(_run(lambda: _lib().dp_nt_gemm(C.byref(p), _stream()), _nt_name(p), 2.0 * N * Co * K), 'dp_nt_gemm(linear)')
