@@ -80,6 +80,11 @@ class Ups9Params(C.Structure):
                                                                                          'accumulate', 'tile')]
 
 
+class Ups9FwdParams(C.Structure):
+    _fields_ = [('U', C.c_void_p), ('x', C.c_void_p), ('bias', C.c_void_p), ('y', C.c_void_p), ('x_img_stride', LL), ('y_img_stride', LL),
+                ('u_bytes', C.c_uint), ('x_bytes', C.c_uint)] + [(n, C.c_int) for n in ('ldu', 'N', 'M', 'K', 'H', 'W')]
+
+
 class ColsumItem(C.Structure):
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('N', C.c_int), ('C', C.c_int), ('wstride', C.c_int),
                 ('woff', C.c_int), ('accumulate', C.c_int), ('ld', C.c_int)]
@@ -148,6 +153,7 @@ SIGNATURES = {
     'dp_ups9_u': [_vp, _ll, _vp, _vp],
     'dp_ups9_dgrad': [C.POINTER(Ups9Params), _vp],
     'dp_ups9_dgrad_supported': [C.POINTER(Ups9Params)],
+    'dp_ups9_fwd': [C.POINTER(Ups9FwdParams), _vp],
     'dp_wg_reduce': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp],
     'dp_gather_add': [_vp, _vp, _i, _vp, _vp],
     'dp_group_score': [C.POINTER(ScoreMember), _i, _i, _vp, _vp, _vp, _vp],

@@ -6,7 +6,8 @@
 // y[2i] = m0 + m1, y[2i+1] = m1 + m2.  In two dimensions U = G w G^T (3x3 per (co, ci), integer combinations, dp_ups9_u) with
 // G = [1 0 0; 1 1 1; 0 0 1], and nine products per pixel.
 //
-// This file holds the INPUT GRADIENT of that form (the forward and the weight gradient keep the class launches):
+// This file holds the INPUT GRADIENT and the FORWARD pass of that form (ups9_fwd_kernel, further down); the weight gradient keeps the class
+// launches.  The input gradient:
 //     dx[n][ci][i][j] = sum_co sum_{a,b} U[co][ci][a][b] T[n][co][a][b][i][j],   T = R p R^T,
 // p = the 4x4 patch of the HIGH-resolution dy at rows 2i-1 .. 2i+2 / columns 2j-1 .. 2j+2 (zero outside the image) and
 // R = [0 -1 0 1; 0 1 1 0; 1 0 -1 0] (T0 = p3 - p1, T1 = p1 + p2, T2 = p0 - p2 along each axis): one implicit GEMM with nine taps
@@ -20,6 +21,8 @@
 // inner loop is the plain v_mfma_f32_32x32x2_f32 loop of csrc/gemm.hip over 9 * KC k-steps.  fp32 everywhere, no atomics, one
 // workgroup per output tile, every loop bounded by its arguments: the same bits from run to run.
 #include "dp_common.h"
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define U9_RSRC_FLAGS 0x00020000
 #define U9_OOB 0x80000000u
@@ -232,6 +235,203 @@ extern "C" int dp_ups9_dgrad(const dp_ups9_params* pp, void* stream) {
     if (p.tile == 0)      DP_LAUNCH((ups9_dgrad_kernel<128, 32, 8, 4, 1, 2>), grid, dim3(256), 0, st, p);
     else if (p.tile == 1) DP_LAUNCH((ups9_dgrad_kernel<128, 64, 4, 2, 2, 3>), grid, dim3(256), 0, st, p);
     else                  DP_LAUNCH((ups9_dgrad_kernel<128, 128, 4, 2, 2, 2>), grid, dim3(256), 0, st, p);
+    return DP_LAUNCH_CHECK();
+}
+
+// ---- forward: y[n][co][2i+ph][2j+pw] = (A^T M A)[ph][pw] (+ bias[co]), M[a][b] = sum_ci U[co][ci][a][b] V[n][ci][a][b][i][j] ----------------
+// V = the 3x3 low-resolution patch of x round (i, j), zero outside the image, after (p0 - p1, p1, p2 - p1) along each axis.  Nine
+// implicit GEMMs that share nothing but the patch: a 256-thread workgroup owns BM output channels x BN pixels as four 32x32 tiles, one
+// per wavefront, and every wavefront keeps all nine accumulators of its tile (144 registers), so that the A^T M A epilogue stays in
+// registers and y goes straight to its high-resolution positions, the two pw neighbours as one 8-byte store: no q[4, ...] staging
+// buffer, no interleave pass.  U: dp_pack_weight mode 0 of U ([tap][ci][ld]) -> As[tap * KC + k][m]; V -> Vs[tap * KC + k][pixel].
+template <int BM, int BN, int KC, int OCC>
+__global__ __launch_bounds__(256, OCC) void ups9_fwd_kernel(const dp_ups9_fwd_params p) {
+    constexpr int WN = BN / 32;                     // wavefronts along the pixels
+    constexpr int KT = 9 * KC;
+    constexpr int PT = BN * KC / 256;               // patches per thread and K tile
+    constexpr int KSTEP = 256 / BN;
+    constexpr int MCH = BM / 4;
+    constexpr int ACH = KT * MCH;
+    constexpr int NA = (ACH + 255) / 256;
+    constexpr int NS = 9 * KC / 2;                  // MFMA steps of one K tile
+    static_assert((BM / 32) * WN == 4 && PT >= 1 && BN * KC % 256 == 0 && KC % 2 == 0 && BM % 32 == 0 && BN % 32 == 0, "tile");
+    __shared__ __attribute__((aligned(16))) float As[KT * BM];
+    __shared__ __attribute__((aligned(16))) float Vs[KT * BN];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 31, lk = lane >> 5;
+    const int wm0 = (wave / WN) * 32, wn0 = (wave % WN) * 32;
+    const int H = p.H, W = p.W, HW = H * W;
+    const int K = p.K, M = p.M;
+    const int NPIX = p.N * HW;
+    // row tiles of one pixel block back to back on one XCD (they gather the same patches)
+    const int MT = (M + BM - 1) / BM;
+    const int PTILES = (NPIX + BN - 1) / BN;
+    int mt, ptile;
+    {
+        const int b = blockIdx.x;
+        if (!(PTILES & 7)) {
+            const int xcd = b & 7, slot = b >> 3;
+            mt = slot % MT;
+            ptile = (slot / MT) * 8 + xcd;
+        } else {
+            mt = b % MT;
+            ptile = b / MT;
+        }
+    }
+    const int m0 = mt * BM, px0 = ptile * BN;
+
+    // ---- this thread's patch: pixel tid % BN, channels tid / BN + KSTEP * q of every K tile
+    const int ppix = tid % BN, pk0 = tid / BN;
+    int pbase;                                       // float offset of patch element (0, 0) of channel 0 (may be negative: never used then)
+    bool pvalid, top, bot, left, right;
+    {
+        const int pixel = px0 + ppix;
+        pvalid = pixel < NPIX;
+        const int n = pixel / HW, rem = pixel - n * HW;
+        const int i = rem / W, j = rem - i * W;
+        pbase = (int)(n * p.x_img_stride) + (i - 1) * W + (j - 1);
+        top = i > 0, bot = i < H - 1, left = j > 0, right = j < W - 1;
+    }
+    const __amdgpu_buffer_rsrc_t rA = u9_rsrc(p.U, p.u_bytes);
+    const __amdgpu_buffer_rsrc_t rB = u9_rsrc(p.x, p.x_bytes);
+
+    float pr[PT][9];
+    f32x4 ar[NA];
+    auto load_tile = [&](int k0) {
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const int e = tid + 256 * j;
+            const int kk = e / MCH, m = m0 + 4 * (e % MCH);
+            const int tap = kk / KC, k = k0 + kk % KC;
+            const bool v = e < ACH && m < p.ldu && k < K;
+            ar[j] = u9_bload4(rA, v ? (unsigned)(((tap * K + k) * p.ldu + m) * 4) : U9_OOB);
+        }
+#pragma unroll
+        for (int q = 0; q < PT; ++q) {
+            const int k = k0 + pk0 + KSTEP * q;
+            const bool ok = pvalid && k < K;
+            const int off0 = pbase + k * HW;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const bool rok = ok && (r == 0 ? top : r == 2 ? bot : true);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const bool v = rok && (c == 0 ? left : c == 2 ? right : true);
+                    pr[q][3 * r + c] = u9_bload(rB, v ? (unsigned)((off0 + r * W + c) * 4) : U9_OOB);
+                }
+            }
+        }
+    };
+    auto store_tile = [&]() {
+#pragma unroll
+        for (int j = 0; j < NA; ++j)
+            if (NA * 256 == ACH || tid + 256 * j < ACH) *(f32x4*)&As[(tid + 256 * j) * 4] = ar[j];
+#pragma unroll
+        for (int q = 0; q < PT; ++q) {
+            const float* d = pr[q];
+            float t[3][3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                t[0][c] = d[c] - d[3 + c];
+                t[1][c] = d[3 + c];
+                t[2][c] = d[6 + c] - d[3 + c];
+            }
+            const int kc = pk0 + KSTEP * q;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                Vs[((3 * a + 0) * KC + kc) * BN + ppix] = t[a][0] - t[a][1];
+                Vs[((3 * a + 1) * KC + kc) * BN + ppix] = t[a][1];
+                Vs[((3 * a + 2) * KC + kc) * BN + ppix] = t[a][2] - t[a][1];
+            }
+        }
+    };
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    const int nIter = (K + KC - 1) / KC;
+    load_tile(0);
+    for (int it = 0; it < nIter; ++it) {
+        __syncthreads();                             // the MFMAs of the previous tile have read their operands
+        store_tile();
+        __syncthreads();
+        if (it + 1 < nIter) load_tile((it + 1) * KC);        // in flight during the MFMAs below
+        // step s = (k pair s / 9, tap s % 9); fragment reads two steps ahead of the MFMA that consumes them
+        float a[3], b[3];
+        auto frag = [&](int s, float& fa, float& fb) {
+            const int kk = (s % 9) * KC + (s / 9) * 2 + lk;
+            fa = As[kk * BM + wm0 + li];
+            fb = Vs[kk * BN + wn0 + li];
+        };
+        frag(0, a[0], b[0]);
+        frag(1, a[1], b[1]);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            if (s + 2 < NS) frag(s + 2, a[(s + 2) % 3], b[(s + 2) % 3]);
+            __builtin_amdgcn_sched_barrier(0);
+            acc[s % 9] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s % 3], b[s % 3], acc[s % 9], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+
+    // ---- epilogue.  C/D map of a 32x32 tile: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    const int pixel = px0 + wn0 + li;
+    if (pixel >= NPIX) return;
+    const int n = pixel / HW, rem = pixel - n * HW;
+    const int i = rem / W, j = rem - i * W;
+    float* o = p.y + (long long)n * p.y_img_stride + (long long)(2 * i) * (2 * W) + 2 * j;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        if (row < M) {
+            const float bv = p.bias ? p.bias[row] : 0.f;
+            const float c0 = acc[0][r] + acc[3][r], c1 = acc[1][r] + acc[4][r], c2 = acc[2][r] + acc[5][r];      // rows a = 0, 1
+            const float d0 = acc[3][r] + acc[6][r], d1 = acc[4][r] + acc[7][r], d2 = acc[5][r] + acc[8][r];      // rows a = 1, 2
+            float* q = o + (long long)row * (4 * HW);
+            f32x2 y0, y1;
+            y0[0] = (c0 + c1) + bv, y0[1] = (c1 + c2) + bv;
+            y1[0] = (d0 + d1) + bv, y1[1] = (d1 + d2) + bv;
+            *(f32x2*)q = y0;
+            *(f32x2*)(q + 2 * W) = y1;
+        }
+    }
+}
+
+// One tile: 64 output channels x 64 pixels, 8 input channels per K tile.  [measured, profiles/ups9_fwd_gate.txt: a 128 x 32 tile (4 channels
+// per K tile, 8 would spill) was slower on every row, by 25 % at the pruned widths, which pad 180 rows to 256 instead of 192.]
+#define U9F_BM 64
+#define U9F_BN 64
+
+// What dp_ups9_fwd takes (ops.ups9_fwd_shape_ok restates it argument by argument); everything else is hipErrorInvalidValue, nothing launched.
+static bool u9f_ok(const dp_ups9_fwd_params& p) {
+    if (!p.U || !p.x || !p.y || ((uintptr_t)p.U & 15) || ((uintptr_t)p.y & 7) || ((uintptr_t)p.bias & 3)) return false;
+    if (p.N < 1 || p.M < 1 || p.K < 1 || p.H < 1 || p.W < 1) return false;
+    if (p.ldu < p.M || (p.ldu & 3)) return false;
+    const long long HW = (long long)p.H * p.W;
+    const long long npix = HW * p.N;
+    if (npix >= (1ll << 29)) return false;                                             // pixel numbers and block counts are ints
+    if (9ll * p.K * p.ldu * 4 != (long long)p.u_bytes || p.u_bytes >= 0x80000000u) return false;      // U is exactly [9][K][ldu]
+    if (p.x_img_stride < HW * p.K || p.y_img_stride < 4 * HW * p.M || (p.y_img_stride & 1)) return false;      // no overlap; 8-byte stores
+    const long long x_need = ((p.N - 1) * p.x_img_stride + HW * p.K) * 4;
+    if ((long long)p.x_bytes < x_need || p.x_bytes >= 0x80000000u) return false;      // 32-bit byte offsets, bit 31 = out of range
+    const long long blocks = ((npix + U9F_BN - 1) / U9F_BN) * ((p.M + U9F_BM - 1) / U9F_BM);
+    if (blocks >= (1ll << 31)) return false;
+    return true;
+}
+
+extern "C" int dp_ups9_fwd(const dp_ups9_fwd_params* pp, void* stream) {
+    const dp_ups9_fwd_params& p = *pp;
+    if (!u9f_ok(p)) return (int)hipErrorInvalidValue;
+    const long long npix = (long long)p.N * p.H * p.W;
+    const dim3 grid((unsigned)(((npix + U9F_BN - 1) / U9F_BN) * ((p.M + U9F_BM - 1) / U9F_BM)));
+    static_assert(U9F_BM == 64 && U9F_BN == 64, "the launch below names its tile");
+    DP_LAUNCH((ups9_fwd_kernel<64, 64, 8, 2>), grid, dim3(256), 0, (hipStream_t)stream, p);
     return DP_LAUNCH_CHECK();
 }
 

@@ -102,7 +102,7 @@ class _Packs:
             buf, ld = ops.pack_weight_wino(w, mode[1])
         elif isinstance(mode, tuple) and mode[0] == 'wino2d':  # ('wino2d', 0 | 1): Winograd F(2x2, 3x3) operand (ops.pack_weight_wino2d)
             buf, ld = ops.pack_weight_wino2d(w, mode[1])
-        elif isinstance(mode, tuple) and mode[0] == 'up9':     # ('up9', 0, 1): dgrad operand of U = G w G^T (ops.ups9_u, csrc/ups9.hip)
+        elif isinstance(mode, tuple) and mode[0] == 'up9':     # ('up9', 0, 0 | 1): forward / dgrad operand of U = G w G^T (ops.ups9_u)
             self.lazy[(name, mode)] = True
             buf, ld = ops.pack_weight(self.get_u9(name, w), mode[2])
         elif isinstance(mode, tuple) and mode[0] == 'up':      # ('up', class, 0 | 1): class kernel of an upsample convolution
@@ -536,10 +536,16 @@ class UNetEngine:
     # ---- Upsample2D: nearest x2 + conv3x3 (resnet.py:131-166) as four 2x2 convolutions on the low-resolution input --------
     # One per parity class of the output position, with class kernels that are sums of the 3x3 taps reading the same source
     # pixel (csrc/elementwise.hip, dp_ups_weff): the same function with 16 instead of 36 multiply-adds per low-resolution
-    # pixel and channel pair, in the forward pass, the input gradient and the weight gradient alike.
+    # pixel and channel pair, in the forward pass, the input gradient and the weight gradient alike.  Where the measured gates take the
+    # shape (ops.ups9_fwd_wanted / ops.ups9_dgrad_wanted), the forward pass and the input gradient run in NINE products per pixel
+    # instead (U = G w G^T, csrc/ups9.hip): one launch each, reading x / dy and writing y / dx where they lie, so that the forward has
+    # no class staging buffer and no interleave pass.  The weight gradient keeps the class form.
     def _ups_conv_fwd(self, name, x):
         w = self.P[name + '.weight']
         N, _, H, W = x.shape
+        if hasattr(ops, 'ups9_fwd_wanted') and ops.ups9_fwd_wanted(N, w.shape[1], w.shape[0], H, W):
+            up, ldu = self.packs.get(name, w, ('up9', 0, 0))
+            return ops.ups9_fwd(x, up, ldu, w.shape[0], bias=self.P.get(name + '.bias'))
         q = ops.empty_act((4, N, w.shape[0], H, W), x.device)
         for c, spec in enumerate(_UPS_SPECS):
             wp, ld = self.packs.get(name, w, ('up', c, 0))

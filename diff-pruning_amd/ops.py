@@ -862,6 +862,84 @@ def ups9_dgrad(dy, up, ldu, Cin, *, out=None, accumulate=False, tile=None):
     return out
 
 
+# ---- ... and the forward pass (dp_ups9_fwd): y written straight to its high-resolution positions
+UPS9_FWD_TILE = (64, 64)                                     # (output channels, pixels) per workgroup of dp_ups9_fwd
+_UPS9_FWD_NAME = 'ups9_fwd_kernel<64, 64, 8, 2>'
+UPS9_FWD_GATE_MIN_BLOCKS, UPS9_FWD_GATE_MAX_CH = 96, 256     # (see ups9_fwd_gate)
+
+
+def ups9_fwd_shape_ok(N, Cin, Cout, H, W, x_img_stride, y_img_stride, x_bytes, ldu, u_bytes, u_ptr=0, y_ptr=0, bias_ptr=0):
+    """The same rule as dp_ups9_fwd applies before it launches (u9f_ok, csrc/ups9.hip), argument by argument.  H, W: the LOW resolution; strides in floats,
+    extents in bytes."""
+    if min(N, Cin, Cout, H, W) < 1 or (u_ptr & 15) or (y_ptr & 7) or (bias_ptr & 3):
+        return False
+    if ldu < Cout or (ldu & 3):
+        return False
+    HW = H * W
+    npix = HW * N
+    if npix >= (1 << 29):
+        return False
+    if 9 * Cin * ldu * 4 != u_bytes or u_bytes >= _MAX_BYTES:
+        return False
+    if x_img_stride < HW * Cin or y_img_stride < 4 * HW * Cout or (y_img_stride & 1):
+        return False
+    if x_bytes < ((N - 1) * x_img_stride + HW * Cin) * 4 or x_bytes >= _MAX_BYTES:
+        return False
+    bm, bn = UPS9_FWD_TILE
+    return -(-npix // bn) * -(-Cout // bm) < (1 << 31)
+
+
+def ups9_fwd_gate(N, Cin, Cout, H, W):
+    """Shape classes on which dp_ups9_fwd beat the four class launches plus their interleave pass (tools/bench_ups9.py --pass fwd,
+    profiles/ups9_fwd_gate.txt); everything else keeps the class launches.  [measured, ms per call, class launches + interleave ->
+    dp_ups9_fwd: batch 256 x 256 channels 0.158 -> 0.067 (4x4), 0.342 -> 0.212 (8x8), 1.128 -> 0.811 (16x16); pruned 180 channels x batch
+    128: 0.088 -> 0.048 (96 workgroups), 0.170 -> 0.079, 0.371 -> 0.228; bedroom256's 4 images: 256 ch @ 32x32 0.149 -> 0.063, @ 64x64
+    0.343 -> 0.191, 128 ch @ 128x128 0.343 -> 0.200; but 512 ch @ 8x8 0.118 -> 0.123 (32 workgroups), and @ 16x16 0.139 -> 0.122 (128
+    workgroups) is left with the input gradient's limit of 256 channels.]"""
+    bm, bn = UPS9_FWD_TILE
+    blocks = -(-(N * H * W) // bn) * -(-Cout // bm)
+    return blocks >= UPS9_FWD_GATE_MIN_BLOCKS and max(Cin, Cout) <= UPS9_FWD_GATE_MAX_CH
+
+
+def ups9_fwd_wanted(N, Cin, Cout, H, W):
+    """Host gate of the nine-product forward: DP_UPS9 and the measured table.  Shapes only -- the caller's tensors are checked again,
+    strides and extents included, by ups9_fwd_shape_ok at the launch."""
+    if not UPS9 or min(N, Cin, Cout, H, W) < 1 or N * H * W * max(Cin, 4 * Cout) * 4 >= _MAX_BYTES:
+        return False
+    return ups9_fwd_gate(N, Cin, Cout, H, W)
+
+
+def _ups9_fwd_params(x, up, ldu, Cout, bias, out):
+    sx, so = _chk_act(x), _chk_act(out)
+    N, Cin, H, W = x.shape
+    p = L.Ups9FwdParams()
+    p.U, p.x, p.bias, p.y = _p(up), _p(x), _p(bias), _p(out)
+    p.x_img_stride, p.y_img_stride = sx, so
+    p.u_bytes, p.x_bytes = up.numel() * 4, _extent_bytes(x)
+    p.ldu, p.N, p.M, p.K, p.H, p.W = ldu, N, Cout, Cin, H, W
+    return p
+
+
+def ups9_fwd(x, up, ldu, Cout, *, bias=None, out=None):
+    """y[N, Cout, 2H, 2W] = conv3x3(nearest_up2(x), w, pad 1) (+ bias) from the LOW-resolution x[N, Cin, H, W] in nine products per pixel.
+    up / ldu: pack_weight(ups9_u(w), 0).  Raises when the shape rule refuses the launch (callers ask ups9_fwd_wanted first)."""
+    N, Cin, H, W = x.shape
+    if out is None:
+        out = empty_act((N, Cout, 2 * H, 2 * W), x.device)
+    assert out.shape == (N, Cout, 2 * H, 2 * W) and (bias is None or (bias.numel() == Cout and bias.is_contiguous()))
+    p = _ups9_fwd_params(x, up, ldu, Cout, bias, out)
+    ok = ups9_fwd_shape_ok(N, Cin, Cout, H, W, p.x_img_stride, p.y_img_stride, p.x_bytes, ldu, p.u_bytes, up.data_ptr(),
+                           out.data_ptr(), bias.data_ptr() if bias is not None else 0)
+    if not ok:
+        raise ValueError('dp_ups9_fwd does not take this launch (ups9_fwd_shape_ok)')
+    rc = _run(lambda: _lib().dp_ups9_fwd(C.byref(p), _stream()),
+              _UPS9_FWD_NAME,
+              2.0 * Cin * N * H * W * Cout * 9, 4.0 * (x.numel() + up.numel() + out.numel()))
+    assert rc != 1, 'host shape rule and dp_ups9_fwd disagree (hipErrorInvalidValue for a launch ups9_fwd_shape_ok takes)'
+    L.check(rc, 'dp_ups9_fwd')
+    return out
+
+
 _ws_cache = {}
 WGRAD_BLOCKS = 1024         # target workgroups per wgrad launch (256 CUs x 4 resident workgroups)
 WGRAD_MIN_PIX = int(os.environ.get('DP_WGRAD_MIN_PIX', '128'))      # fewest pixels per split-K slice of a weight gradient

@@ -348,6 +348,21 @@ typedef struct dp_ups9_params {
 int dp_ups9_u(const float* w, long long M, float* u, void* stream);
 int dp_ups9_dgrad(const dp_ups9_params* p, void* stream);
 int dp_ups9_dgrad_supported(const dp_ups9_params* p);
+/* dp_ups9_fwd: y[n][co][2i+ph][2j+pw] = (A^T M A)[ph][pw] (+ bias[co]), M[a][b] = sum_ci U[co][ci][a][b] V[a][b], V = the 3x3
+ * low-resolution patch of x[N][K][H][W] round (i, j) (zero outside) after (p0 - p1, p1, p2 - p1) along each axis, A = [1 0; 1 1; 0 1]:
+ * the forward pass written straight to the high-resolution y[N][M][2H][2W] (no class staging buffer, no interleave pass).
+ * U: dp_pack_weight(u, mode 0) -- exactly 9 * K * ldu floats, 16-byte aligned; M = Cout, K = Cin; H, W: the low resolution.
+ * x / y: contiguous images at x_img_stride / y_img_stride floats, y 8-byte aligned and y_img_stride even; x_bytes: readable extent
+ * from x, below 2 GiB; bias: M floats or NULL.  One workgroup per 64 output channels x 64 pixels, one fixed-order sum per output: the
+ * same bits from run to run.  dp_ups9_fwd checks all of this itself and returns hipErrorInvalidValue, launching nothing, for what it does
+ * not take (ops.ups9_fwd_shape_ok is the host's restatement of that rule). */
+typedef struct dp_ups9_fwd_params {
+    const float* U; const float* x; const float* bias; float* y;
+    long long x_img_stride, y_img_stride;
+    unsigned u_bytes, x_bytes;
+    int ldu, N, M, K, H, W;
+} dp_ups9_fwd_params;
+int dp_ups9_fwd(const dp_ups9_fwd_params* p, void* stream);
 
 /* Taylor-importance reductions  (ddpm_exp/torch_pruning/importance.py:375-434).
  * Weight viewed as [R][C][T]; dim = 0: out[r] = sum_{c,t} f(w*g); dim = 1: out[c] = sum_{r,t} f(w*g);

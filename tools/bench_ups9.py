@@ -6,7 +6,10 @@ the class weight gradients while only the input gradient runs in the new form, b
 bedroom256's (4 images per GPU).
 Executed TFLOP/s = 2 * taps * Cin * Cout * pixels / time with taps = 9 (new) or 16 (class launches).
 
-    python tools/bench_ups9.py [--out profiles/ups9_gate.txt] [--check]"""
+With --pass fwd the same table for the forward pass: the four class launches with and without their interleave pass against dp_ups9_fwd
+errors against fp64 conv2d(interpolate(x, 2), w, padding=1).
+
+    python tools/bench_ups9.py [--pass dgrad|fwd] [--out profiles/ups9_gate.txt | profiles/ups9_fwd_gate.txt] [--check]"""
 import argparse
 import importlib
 import os
@@ -36,18 +39,67 @@ def timeit(fn, n=20, reps=3):
     return min(ts), max(ts) - min(ts)
 
 
+SHAPES = [(256, 256, 256, h) for h in (4, 8, 16)] + [(128, 180, 180, h) for h in (4, 8, 16)] + [(128, 179, 179, 16), (256, 128, 128, 16)]
+# bedroom256: 4 images per GPU, 512 / 512 / 256 / 256 / 128 channels at 8 .. 128 low-resolution pixels a side
+SHAPES += [(4, 512, 512, 8), (4, 512, 512, 16), (4, 256, 256, 32), (4, 256, 256, 64), (4, 128, 128, 128)]
+
+
+def forward_table(args, dev):
+    lines = ['forward of Upsample2D\'s convolution: class launches (16 taps) vs dp_ups9_fwd (9 taps, %d x %d tile); ms per call, fastest of 3 windows of 20'
+             % ops.UPS9_FWD_TILE,
+             'shape                       4 class   +interl   | ups9    (TF/s)  | gate  vs 4 class  vs +interl  spread']
+    for (B, Cin, Cout, H) in SHAPES:
+        w = torch.randn(Cout, Cin, 3, 3, device=dev) / (3.0 * Cin ** 0.5)
+        bias = torch.randn(Cout, device=dev)
+        x = ops.empty_act((B, Cin, H, H), dev).normal_()
+        weff = ops.ups_weff(w)
+        cls = [ops.pack_weight(weff[c], 0) for c in range(4)]
+        up, ldu = ops.pack_weight(ops.ups9_u(w), 0)
+        q = ops.empty_act((4, B, Cout, H, H), dev)
+        y9 = ops.empty_act((B, Cout, 2 * H, 2 * H), dev)
+
+        def class4():
+            for c, spec in enumerate(ops.UPS_CLASS_SPECS):
+                ops.conv_forward(x, None, cls[c][0], cls[c][1], Cout, spec, bias=bias, out=q[c])
+
+        def class4_interleave():
+            class4()
+            return ops.interleave2x2(q)
+
+        t4, _ = timeit(class4)
+        t4i, s4 = timeit(class4_interleave)
+        t9, s9 = timeit(lambda: ops.ups9_fwd(x, up, ldu, Cout, bias=bias, out=y9))
+        line = 'B%-3d %3d->%3d @%2dx%-2d        %.4f    %.4f   |  %.4f (%5.1f) | %-4s  %.2fx      %.2fx      %.4f / %.4f' % (
+            B, Cin, Cout, H, H, t4, t4i, t9, 2.0 * 9 * Cin * Cout * B * H * H / t9 / 1e9, 'on' if ops.ups9_fwd_gate(B, Cin, Cout, H, H) else 'off',
+            t4 / t9, t4i / t9, s4, s9)
+        if args.check:
+            nb = min(B, 8)
+            ref = torch.nn.functional.conv2d(torch.nn.functional.interpolate(x[:nb].double(), scale_factor=2, mode='nearest'), w.double(),
+                                             bias.double(), padding=1)
+            errs = [float((t[:nb].double() - ref).abs().max() / ref.abs().max()) for t in (class4_interleave(), y9)]
+            line += '   err class %.1e  ups9 %.1e' % tuple(errs)
+        lines.append(line)
+        print(line, flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
-    ap.add_argument('--check', action='store_true', help='also print each form\'s error against fp64 autograd (8 images)')
+    ap.add_argument('--pass', dest='which', default='dgrad', choices=('dgrad', 'fwd'))
+    ap.add_argument('--check', action='store_true', help='also print each form\'s error against fp64 (8 images)')
     args = ap.parse_args()
     dev = torch.device('cuda')
+    if args.which == 'fwd':
+        lines = forward_table(args, dev)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+        return
     lines = ['input gradient of Upsample2D\'s convolution: class launches (16 taps) vs dp_ups9_dgrad (9 taps); ms per call, fastest of 3 windows of 20',
              'shape                       4 class   +deint    | ups9 t32 (TF/s)   t64 (TF/s)   t128 (TF/s) | default tile  vs 4 class  vs +deint  spread']
-    shapes = [(256, 256, 256, h) for h in (4, 8, 16)] + [(128, 180, 180, h) for h in (4, 8, 16)] + [(128, 179, 179, 16), (256, 128, 128, 16)]
-    # bedroom256: 4 images per GPU, 512 / 512 / 256 / 256 / 128 channels at 8 .. 128 low-resolution pixels a side
-    shapes += [(4, 512, 512, 8), (4, 512, 512, 16), (4, 256, 256, 32), (4, 256, 256, 64), (4, 128, 128, 128)]
-    for (B, Cin, Cout, H) in shapes:
+    for (B, Cin, Cout, H) in SHAPES:
         w = torch.randn(Cout, Cin, 3, 3, device=dev) / (3.0 * Cin ** 0.5)
         dy = ops.empty_act((B, Cout, 2 * H, 2 * H), dev).normal_()
         weff = ops.ups_weff(w)
