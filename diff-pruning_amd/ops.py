@@ -91,7 +91,19 @@ def _conv_x4_ok(p):
     return g.Wo % 4 == 0 and g.Ws >= 4 and 0 <= g.pad_l <= 1 and 0 <= g.kw - 1 - g.pad_l <= 1
 
 
+def _conv_few_out_ok(p):
+    """Same rule as conv_few_out_ok() in csrc/gemm.hip: dp_conv_gemm runs a <= 4-output-channel 3x3 'same' convolution with nothing but a
+    bias in its epilogue on the direct stencil kernel, whatever tile the block names."""
+    g = p.g
+    return (p.M <= 4 and p.lda == 4 and not p.a_kc and p.ntaps == 9 and g.kw == 3 and g.stride == 1 and g.sden == 1 and g.ups == 0
+            and g.pad_t == 1 and g.pad_l == 1 and g.Ho == g.Hs and g.Wo == g.Ws and g.Hs == g.Hv and g.Ws == g.Wv and not p.X2
+            and not p.tadd and not p.res and not p.accumulate and p.ksplit <= 1 and p.batches <= 1 and p.NPIX % (g.Ho * g.Wo) == 0
+            and not os.environ.get('DP_NO_FEW_OUT'))
+
+
 def _cg_name(p):
+    if p.M <= 4 and _conv_few_out_ok(p):
+        return 'conv_few_out_kernel'
     if p.tile == 4 and _conv_fast_ok(p) and _conv_x4_ok(p) and p.C % 16 == 0 and not (bool(p.X2) and p.g.c_split % 16):
         return 'conv_gemm_fast_kernel<128, 64, false, true>'
     if p.tile in (0, 3, 4) and _conv_fast_ok(p):

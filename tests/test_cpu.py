@@ -1,6 +1,7 @@
 """CPU suite (`-m "not gpu"`): the oracle against the reference's golden vectors, the host logic (group
 enumeration, schedules, pruner bookkeeping) and the C-ABI library surface.  No GPU compute is called."""
 import ctypes
+import math
 import os
 import re
 
@@ -34,24 +35,67 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_every_launch_site_of_the_tabled_files_is_in_the_branch_table():
-    """tests/test_dispatch_parity_gpu.py compares every dispatch branch of these files with fp64.  A new DP_LAUNCH site changes the
-    count recorded there, a new kernel name is in none of its tables: either fails here, before a GPU is needed, so the table
-    is edited (and a case written) together with the launcher."""
+    """tests/test_dispatch_parity_gpu.py (the non-contraction launchers) and tests/test_contraction_dispatch_gpu.py (the contraction
+    kernels) compare every dispatch branch of their files with fp64.  A new DP_LAUNCH site changes the count recorded there, a new
+    kernel name is in none of the tables, a new .hip file with launches is in neither: each fails here, before a GPU is needed, so the
+    table is edited (and a case written) together with the launcher."""
+    import test_contraction_dispatch_gpu as K
     import test_dispatch_parity_gpu as D
     csrc = os.path.join(ROOT, 'diff-pruning_amd', 'csrc')
-    tabled = {e.split(' | ')[0].split('<')[0] for e in D.BRANCHES}
-    assert not set(D.UNREACHED) - set(D.BRANCHES)
-    seen = set()
-    for fname, want in D.LAUNCH_SITES.items():
-        src = open(os.path.join(csrc, fname)).read()
-        sites = re.findall(r'\bDP_LAUNCH\(\(?\s*([A-Za-z_]\w*)', src)
-        assert len(sites) == want == src.count('DP_LAUNCH('), (fname, len(sites), want)
-        seen |= set(sites)
-    assert seen == tabled, (sorted(seen - tabled), sorted(tabled - seen))
-    assert all(e in D.CASES or e in D.UNREACHED for e in D.BRANCHES) and not set(D.CASES) & set(D.UNREACHED)
+    names = {}
+    for T in (D, K):
+        tabled = {e.split(' | ')[0].split('<')[0] for e in T.BRANCHES}
+        assert not set(T.UNREACHED) - set(T.BRANCHES)
+        seen = {}
+        for fname, want in T.LAUNCH_SITES.items():
+            src = open(os.path.join(csrc, fname)).read()
+            sites = re.findall(r'\bDP_LAUNCH\(\(?\s*([A-Za-z_]\w*)', src)
+            assert len(sites) == want == src.count('DP_LAUNCH('), (fname, len(sites), want)
+            seen.update({k: fname for k in sites})
+        assert set(seen) == tabled, (T.__name__, 'launched, not tabled: %s' % sorted((seen[k], k) for k in set(seen) - tabled),
+                                     'tabled, not launched: %s' % sorted(tabled - set(seen)))
+        assert all(e in T.CASES or e in T.UNREACHED for e in T.BRANCHES) and not set(T.CASES) & set(T.UNREACHED), T.__name__
+        assert all(r.strip() for r in T.UNREACHED.values())
+        names[T] = tabled
+    # the two tables together cover exactly the files that launch anything, and no kernel is tabled twice
+    launching = {f for f in os.listdir(csrc) if f.endswith('.hip') and 'DP_LAUNCH(' in open(os.path.join(csrc, f)).read()}
+    assert not set(D.LAUNCH_SITES) & set(K.LAUNCH_SITES)
+    assert set(D.LAUNCH_SITES) | set(K.LAUNCH_SITES) == launching, sorted(launching ^ (set(D.LAUNCH_SITES) | set(K.LAUNCH_SITES)))
+    assert not names[D] & names[K], sorted(names[D] & names[K])
+    assert not {e.split(' | ')[0] for e in D.BRANCHES} & {e.split(' | ')[0] for e in K.BRANCHES}
     # the ring records the kernel expression of the launch site: its first macro argument, stringised
     hdr = open(os.path.join(csrc, 'dp_common.h')).read()
     assert re.search(r'#define DP_LAUNCH\(k, \.\.\.\).*= #k;.*hipLaunchKernelGGL\(k, __VA_ARGS__\)', hdr)
+
+
+def test_contraction_dispatch_comparison_and_name_mirror():
+    """The comparison tests/test_contraction_dispatch_gpu.py judges every case with (helpers.relerr: max-abs error over the reference's
+    max-abs, then exceeding): a reference equal to the output passes, one element moved by twice the bound fails, a NaN in the output
+    fails; and the one normalisation between a launch site's expression and ops._run's name."""
+    import test_contraction_dispatch_gpu as K
+    g = torch.Generator().manual_seed(3)
+    y = torch.randn(3, 5, 7, generator=g)
+    for bound in (K.B_WINO, K.B_DIRECT, 0.0):
+        ok = dict(names=[], out=relerr(y, y.double()), bound=bound)
+        assert not K.exceeding(ok), ok
+        ref = y.double().clone()
+        ref[1, 2, 3] += 2 * max(bound, 1e-7) * float(ref.abs().max())
+        moved = dict(names=[], out=relerr(y, ref), bound=bound)
+        assert list(K.exceeding(moved)) == ['out'] and moved['out'] > bound, moved
+        bad = y.clone()
+        bad[2, 4, 6] = float('nan')
+        nan = dict(names=[], out=relerr(bad, y.double()), other=0.0, bound=bound)
+        assert list(K.exceeding(nan)) == ['out'] and math.isnan(nan['out']), nan
+    m = K.mirror_matches
+    assert m('conv_gemm_kernel<BM, BN, false, true>', 'conv_gemm_kernel<64, 128, false, true>')
+    assert not m('conv_gemm_kernel<BM, BN, false, true>', 'conv_gemm_kernel<64, 128, false, false>')
+    assert m('conv_gemm_fast_kernel<BM, 128, TAILS, true>', 'conv_gemm_fast_kernel<96, 128, true, true>')
+    assert not m('conv_gemm_fast_kernel<BM, 128, TAILS, true>', 'conv_gemm_fast_kernel<128, 64, false, true>')
+    assert m('nt_gemm_kernel<BM, BN, true>', 'nt_gemm_kernel<128, 128, true, false>') and not m('nt_gemm_kernel<BM, BN, true>', 'nt_gemm_kernel<128, 128, true, true>')
+    assert m('nt_gemm_kernel<64, 64, false, true>', 'nt_gemm_kernel<64, 64, false, true>') and not m('nt_gemm_kernel<64, 64, false, true>', 'nt_gemm_kernel<64, 64, false, false>')
+    assert m('conv_wino_kernel<16, 2>', 'conv_wino_kernel<16, 2, 1>') and not m('conv_wino_kernel<16, 2>', 'conv_wino_kernel<16, 2, 2>')
+    assert not m('conv_wino_kernel<16, 2>', 'conv_wino_kernel<8, 2, 1>') and not m('conv_wino2d_kernel<8, 2, false>', 'conv_wino2d_tail_kernel<8, 2, false>')
+    assert m('conv_few_out_kernel', 'conv_few_out_kernel') and not m('conv_few_out_kernel', 'conv_gemm_kernel<64, 64, false, false>')
 
 
 def test_diffusers_pipeline_directory_io(tmp_path):

@@ -1,7 +1,8 @@
 """Parity with fp64 on every dispatch branch of the non-contraction kernels.
 
-The launchers of csrc/norm.hip, transformer.hip, elementwise.hip, importance.hip, optim.hip and vq.hip choose a kernel, a template
-instantiation or a vector path from the shape, the alignment and the optional operands.  Every launch records the kernel expression
+The launchers of csrc/norm.hip, transformer.hip, elementwise.hip, importance.hip, optim.hip, vq.hip, sampler.hip, ldm_sampler.hip and
+ema.hip choose a kernel, a template instantiation or a vector path from the shape, the alignment and the optional operands (the
+contraction kernels have the same tables in tests/test_contraction_dispatch_gpu.py).  Every launch records the kernel expression
 of its launch site (DP_LAUNCH in csrc/dp_common.h, read back through dp_recent_launches), so a case can state which branch it took:
 
   BRANCHES    every name (or `name | condition` where a runtime flag rather than the name selects the path) the tabled launch
@@ -32,7 +33,8 @@ DEV = 'cuda'
 CAP = 8192 * 256                     # dp_grid / tf_grid: at most 8192 workgroups of 256 threads; past it the grid-stride loop turns
 BIG = 3 * CAP + 77                   # "just past a multiple of the cap, with a ragged end"
 
-LAUNCH_SITES = {'norm.hip': 19, 'transformer.hip': 8, 'elementwise.hip': 35, 'importance.hip': 8, 'optim.hip': 8, 'vq.hip': 2}
+LAUNCH_SITES = {'norm.hip': 19, 'transformer.hip': 8, 'elementwise.hip': 35, 'importance.hip': 8, 'optim.hip': 8, 'vq.hip': 2,
+                'sampler.hip': 4, 'ldm_sampler.hip': 2, 'ema.hip': 2}
 
 _GN_ADDS = ('false, false', 'true, false', 'false, true', 'true, true')       # <.., A1, A2>: add1 / add2 present
 BRANCHES = [
@@ -106,6 +108,16 @@ BRANCHES = [
     # ---- vq.hip: one instantiation per embedding width D = 1 .. 16
 ] + ['vq_quantize_kernel<%d>' % d for d in range(1, 17)] + [
     'vq_loss_kernel',
+    # ---- sampler.hip.  16-byte accesses between a scalar head and tail when every pointer has the same 16-byte phase, else 4-byte ones
+    'denoise_step_kernel<0>',                    # mode 0: generalized_steps
+    'denoise_step_kernel<1>',                    # mode 1: ddpm_steps
+    'image_to_u8_kernel<true>',                  # C <= 4, HW % 4 == 0, image stride % 4 == 0, x 16-byte and out 4-byte aligned
+    'image_to_u8_kernel<false>',                 # otherwise
+    # ---- ldm_sampler.hip: <ORDER, GUIDED> (the two sites of CFG_DENOISE_CASE, once per order 0 .. 4); GUIDED = e holds both halves
+] + ['cfg_denoise_step_kernel<%d, %s>' % (o, g) for o in range(5) for g in ('true', 'false')] + [
+    # ---- ema.hip
+    'ema_update_kernel<true>',                   # both buffers 16-byte aligned and n >= 4: 16-byte accesses + a scalar tail
+    'ema_update_kernel<false>',                  # otherwise
 ]
 
 UNREACHED = {}
@@ -1393,6 +1405,171 @@ def _reg_vq():
 
 
 _reg_vq()
+
+
+# ======================================================================================================================
+# the sampler updates and the EMA (sampler.hip, ldm_sampler.hip, ema.hip): flat buffers at every alignment the launchers tell apart
+# ======================================================================================================================
+NAN = float('nan')
+
+
+def _at(n, off, seed=None, scale=1.0):
+    """n floats that start `off` floats behind a 16-byte boundary (random, or NaN for an output) and the buffer they lie in."""
+    buf = torch.full((n + 8,), NAN, device=DEV) if seed is None else rnd(n + 8, seed=seed, scale=scale)
+    return buf[4 + off:4 + off + n], buf
+
+
+def _rest_is_nan(buf, off, n):
+    return bool(buf[:4 + off].isnan().all()) and bool(buf[4 + off + n:].isnan().all())
+
+
+# (n, the offset of every pointer, the offset of eps alone).  16-byte path with a 1-element tail / below one float4 / three trips of
+# the grid-stride loop + a tail / a shared phase of 4 bytes: a 3-element head / eps on another phase: 4-byte accesses throughout
+FLAT_ALIGN = ((77, 0, 0), (3, 0, 0), (BIG, 0, 0), (1003, 1, 1), (1003, 0, 2), (4 * 4096 * 256 + 4099, 3, 0))
+
+
+def _reg_denoise():
+    for mode in (0, 1):
+        @case('denoise_step_kernel<%d>' % mode)
+        def c(ops, mode=mode):
+            coef = (0.79, 0.61, 0.72, 0.11, 0.68) if mode == 0 else (1.64, 1.30, 0.013, 0.985, 1.02, 0.07)
+            for i, (n, off, off_e) in enumerate(FLAT_ALIGN):
+                with_z, with_x0, in_place = i % 3 != 1, i % 2 == 0, i == 3
+                x, e = _at(n, off, 1)[0], _at(n, off_e, 2)[0]
+                z = _at(n, off, 3)[0] if with_z else None
+                (out, obuf), (x0, xbuf) = ((x, None) if in_place else _at(n, off)), (_at(n, off) if with_x0 else (None, None))
+                xr, er, zr = d64(x), d64(e), (d64(z) if with_z else 0.0)
+                _, names = launched(ops, lambda: ops.denoise_step(x, e, mode, coef, z=z, out=out, x0_out=x0))
+                assert names == ['denoise_step_kernel<%d>' % mode], names
+                if mode == 0:
+                    s1, s2, s3, c1, c2 = coef
+                    x0r = (xr - er * s1) / s2
+                    nr = s3 * x0r + c1 * zr + c2 * er
+                else:
+                    r1, r2, k0, kx, dd, sig = coef
+                    x0r = (r1 * xr - r2 * er).clamp(-1, 1)
+                    nr = (k0 * x0r + kx * xr) / dd + sig * zr
+                assert (in_place or _rest_is_nan(obuf, off, n)) and (not with_x0 or _rest_is_nan(xbuf, off, n))
+                res = dict(names=names, n=n, offsets=(off, off_e), z=with_z, in_place=in_place, next=relerr(out, nr), bound=1e-5)
+                if with_x0:
+                    res['x0'] = relerr(x0, x0r)
+                yield res
+
+
+_reg_denoise()
+
+
+def _image_bytes(x, rescaled):
+    """The torch fp32 expression the kernel restates, operation by operation."""
+    v = ((x + 1.0) / 2.0 if rescaled else x).clamp(0.0, 1.0)
+    return (v * 255.0 + 0.5).clamp(0.0, 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def _image_to_u8(ops, name, x, rescaled):
+    N, C, H, W = x.shape
+    vec = C <= 4 and (H * W) % 4 == 0 and (x.stride(0) if N > 1 else 0) % 4 == 0 and x.data_ptr() % 16 == 0
+    assert name == 'image_to_u8_kernel<%s>' % ('true' if vec else 'false'), (tuple(x.shape), x.stride(), vec)
+    out = torch.full((N * H * W * C + 8,), 77, dtype=torch.uint8, device=DEV)
+    view = out[4:4 + N * H * W * C].view(N, H, W, C)
+    _, names = launched(ops, lambda: ops.image_to_u8(x, rescaled=rescaled, out=view))
+    assert names == [name], names
+    ref = _image_bytes(x.cpu(), rescaled)
+    bad = int((view.cpu() != ref).sum())
+    assert bool((out[:4] == 77).all()) and bool((out[4 + N * H * W * C:] == 77).all())
+    far = int((view.cpu().int() - _image_bytes(d64(x), rescaled).int()).abs().max())          # fp64: at most the next byte
+    assert bad == 0 and far <= 1, (bad, far)
+    return dict(names=names, shape=(N, C, H, W), rescaled=rescaled, mismatches=bad, out=float(bad), bound=0.0)
+
+
+def _beyond(x):
+    """The view itself, scaled in place so that values lie beyond both clamps."""
+    return x.mul_(1.5)
+
+
+@case('image_to_u8_kernel<true>')
+def image_to_u8_vec(ops):
+    """Channel slices of wider buffers, 1 .. 4 channels, values beyond both clamps; 66 planes of 256 x 256: the grid-stride loop turns."""
+    for i, (N, C, H, W) in enumerate(((3, 3, 8, 8), (2, 4, 6, 10), (2, 1, 2, 2), (2, 2, 4, 9), (66, 1, 256, 256))):
+        big = N * H * W > CAP
+        x = _beyond(wide(N, C, H, W, 1, lead=1 if big else 2, extra=1 if big else 6)[0])
+        assert not big or N * (H * W // 4) > 4096 * 256
+        yield _image_to_u8(ops, 'image_to_u8_kernel<true>', x, i % 2 == 0)
+
+
+@case('image_to_u8_kernel<false>')
+def image_to_u8_scalar(ops):
+    """5 channels / HW % 4 != 0 / an image stride that is no multiple of 4 / a view 4 bytes behind a 16-byte boundary / 1.35 M bytes:
+    the grid-stride loop turns."""
+    yield _image_to_u8(ops, 'image_to_u8_kernel<false>', _beyond(wide(2, 5, 8, 8, 1)[0]), True)
+    yield _image_to_u8(ops, 'image_to_u8_kernel<false>', _beyond(wide(3, 3, 5, 3, 1)[0]), False)
+    yield _image_to_u8(ops, 'image_to_u8_kernel<false>', _beyond(rnd(2, 3 * 64 + 1, seed=1)[:, :3 * 64].view(2, 3, 8, 8)), True)
+    yield _image_to_u8(ops, 'image_to_u8_kernel<false>', _beyond(rnd(2 * 3 * 64 + 1, seed=1)[1:].view(2, 3, 8, 8)), True)
+    yield _image_to_u8(ops, 'image_to_u8_kernel<false>', _beyond(wide(5, 3, 299, 301, 1, lead=1, extra=0)[0]), True)
+
+
+def _reg_cfg_denoise():
+    need = (0, 1, 2, 3, 1)
+    for order in range(5):
+        for guided in (True, False):
+            @case('cfg_denoise_step_kernel<%d, %s>' % (order, 'true' if guided else 'false'))
+            def c(ops, order=order, guided=guided):
+                """The guided form reads its conditional half n floats behind the unconditional one: n % 4 != 0 puts it on another phase."""
+                name = 'cfg_denoise_step_kernel<%d, %s>' % (order, 'true' if guided else 'false')
+                coef, scale, temp = (0.63, 0.78, 0.81, 0.52, 0.27), 3.0, 0.9
+                for i, (n, off, off_e) in enumerate(((77, 0, 0), (80, 0, 0), (3, 0, 0), (BIG + 3, 0, 0), (1004, 1, 1), (1003, 0, 2))):
+                    with_z, with_x0, with_eg, in_place = i % 3 != 1, i % 2 == 0, i % 2 == 1 or i == 3, i == 4
+                    x, e = _at(n, off, 1)[0], _at(2 * n if guided else n, off_e, 2)[0]
+                    hist = [_at(n, off, 10 + k)[0] for k in range(need[order])]
+                    z = _at(n, off, 3)[0] if with_z else None
+                    out, obuf = (x, None) if in_place else _at(n, off)
+                    x0, xbuf = _at(n, off) if with_x0 else (None, None)
+                    eg, gbuf = _at(n, off) if with_eg else (None, None)
+                    xr, er, zr = d64(x), d64(e), (d64(z) if with_z else 0.0)
+                    h = [d64(t) for t in hist]
+                    _, names = launched(ops, lambda: ops.cfg_denoise_step(x, e, coef, scale=scale if guided else None, order=order, hist=hist, z=z,
+                                                                          temperature=temp, out=out, x0_out=x0, eg_out=eg))
+                    assert names == [name], names
+                    egr = er[:n] + scale * (er[n:] - er[:n]) if guided else er
+                    epr = (egr, (3 * egr - h[0]) / 2 if order == 1 else None, (23 * egr - 16 * h[0] + 5 * h[1]) / 12 if order == 2 else None,
+                           (55 * egr - 59 * h[0] + 37 * h[1] - 9 * h[2]) / 24 if order == 3 else None, (h[0] + egr) / 2 if order == 4 else None)[order]
+                    s1m, sat, sap, cdir, sigma = coef
+                    x0r = (xr - s1m * epr) / sat
+                    nr = sap * x0r + cdir * epr + sigma * zr * temp
+                    assert (in_place or _rest_is_nan(obuf, off, n)) and (not with_x0 or _rest_is_nan(xbuf, off, n))
+                    assert not with_eg or _rest_is_nan(gbuf, off, n)
+                    res = dict(names=names, n=n, offsets=(off, off_e), z=with_z, in_place=in_place, next=relerr(out, nr), bound=1e-5)
+                    if with_x0:
+                        res['x0'] = relerr(x0, x0r)
+                    if with_eg:
+                        res['eg'] = relerr(eg, egr)
+                    yield res
+
+
+_reg_cfg_denoise()
+
+
+def _ema(ops, name, n, off_s, off_p, decay):
+    (s, sbuf), p = _at(n, off_s, 1), _at(n, off_p, 2)[0]
+    vec = s.data_ptr() % 16 == 0 and p.data_ptr() % 16 == 0 and n >= 4
+    assert name == 'ema_update_kernel<%s>' % ('true' if vec else 'false'), (n, off_s, off_p)
+    sr, pr, before = d64(s), d64(p), sbuf.clone()
+    omd = float(np.float32(1) - np.float32(decay))
+    _, names = launched(ops, lambda: ops.ema_update(s, p, decay))
+    assert names == [name], names
+    assert torch.equal(sbuf[:4 + off_s], before[:4 + off_s]) and torch.equal(sbuf[4 + off_s + n:], before[4 + off_s + n:])
+    return dict(names=names, n=n, offsets=(off_s, off_p), decay=str(decay), out=relerr(s, sr - omd * (sr - pr)), bound=1e-5)
+
+
+@case('ema_update_kernel<true>')
+def ema_vec(ops):
+    for n, decay in ((4, 0.5), (1003, 0.9999), (4096 * 256 * 4 + 1027, 0.5)):                          # the last: second trip + scalar tail
+        yield _ema(ops, 'ema_update_kernel<true>', n, 0, 0, decay)
+
+
+@case('ema_update_kernel<false>')
+def ema_scalar(ops):
+    for n, off_s, off_p, decay in ((3, 0, 0, 0.5), (1003, 1, 1, 0.9999), (1003, 0, 2, 0.5), (4096 * 256 + 77, 3, 0, 0.5)):
+        yield _ema(ops, 'ema_update_kernel<false>', n, off_s, off_p, decay)
 
 
 # ======================================================================================================================
