@@ -186,6 +186,12 @@ SIGNATURES = {
     'dp_ssim': [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
     'dp_ssim_workspace': [_i, _i, _i, _i],
     'dp_mse_per_image': [_vp, _vp, _i, _ll, _vp, _vp],
+    'dp_em_row_norms2': [_vp, _ll, _i, _ll, _vp, _vp],
+    'dp_em_knn_merge': [_vp, _ll, _ll, _ll, _vp, _vp, _i, _i, _vp, _vp],
+    'dp_em_inside_ball': [_vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp],
+    'dp_em_poly_sums': [_vp, _i, _ll, _ll, _ll, _ll, C.c_double, C.c_double, _i, _vp, _i, _vp, _vp],
+    'dp_em_isc_rows': [_vp, _ll, _i, _ll, _vp, _vp, _vp],
+    'dp_em_isc_colmeans': [_vp, _ll, _vp, _ll, _ll, _i, _vp, _vp],
     'dp_vq_blocks': [_ll],
     'dp_vq_quantize': [_vp, _ll, _i, _i, _ll, _vp, _i, _vp, _ll, _vp, _vp, _vp],
     'dp_vq_loss': [_vp, _i, C.c_double, _vp, _vp],

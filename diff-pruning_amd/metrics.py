@@ -496,3 +496,301 @@ def compare_directories(path1, path2, device='cuda', batch_size=100, exts=('png'
         ms.append(mse_per_image(a, b))
     s, m = torch.cat(ss), torch.cat(ms)
     return float(s.mean()), float(m.mean())
+
+
+# ---- Inception Score / KID / precision-recall (ldm_exp/test_diffusion.py: torch_fidelity.calculate_metrics) ------------------
+# torch_fidelity is neither in the reference tree nor installed: its arithmetic is RECALLED, NOT PINNED.  The definitions these
+# functions implement are restated in fp64 in tests/eval_metrics_ref.py; that restatement is the specification.
+# Every N x N quantity is reduced block by block on the device (ops.bmm_nt -> csrc/evalmetrics.hip): no N x N matrix exists
+# anywhere, and only index gathers and the final scalars (numpy float64, as FeatureStats.finalize) are not kernels.
+_GEMM_REACH = 1 << 31               # dp_nt_gemm addresses each operand and its output through 32-bit byte offsets
+KNN_MAX_K = 8                       # neighbourhood size: the kernel keeps k + 1 <= 9 values per lane in registers (DP_EM_MAX_K)
+
+
+def _em_dev(*ts):
+    for t in ts:
+        if t.device.type != 'cuda':
+            raise RuntimeError('the evaluation metrics run on the MI355X HIP kernels only (no CPU / PyTorch fallback)')
+
+
+def _em_mat(g):
+    assert g.dim() == 2 and g.dtype == torch.float32 and (g.stride(1) == 1 or g.shape[1] == 1), 'a row-major fp32 matrix view'
+    return g.shape[0], g.shape[1], (g.stride(0) if g.shape[0] > 1 else max(g.shape[1], 1))
+
+
+def row_norms2(x):
+    """|x_i|^2 per row of an fp32 [n, d] matrix, float64 [n]."""
+    _em_dev(x)
+    n, d, ld = _em_mat(x)
+    out = torch.empty(n, dtype=torch.float64, device=x.device)
+    L.check(L.load().dp_em_row_norms2(ops._p(x), n, d, ld, ops._p(out), ops._stream()), 'dp_em_row_norms2')
+    return out
+
+
+def knn_merge(g, xn, yn, best, first):
+    """best [rows, kk] (fp32, ascending) <- the kk smallest of its old contents (none when `first`) and max(xn_i + yn_j - 2 g_ij, 0)."""
+    _em_dev(g, xn, yn, best)
+    rows, cols, ldg = _em_mat(g)
+    assert xn.dtype == yn.dtype == torch.float64 and xn.is_contiguous() and yn.is_contiguous() and xn.numel() == rows and yn.numel() == cols
+    assert best.dtype == torch.float32 and best.is_contiguous() and best.shape[0] == rows
+    L.check(L.load().dp_em_knn_merge(ops._p(g), rows, cols, ldg, ops._p(xn), ops._p(yn), best.shape[1], 1 if first else 0, ops._p(best),
+                                     ops._stream()), 'dp_em_knn_merge')
+    return best
+
+
+def inside_ball(g, xn, yn, r2, hit):
+    """hit [rows] (int32) |= any_j (max(xn_i + yn_j - 2 g_ij, 0) <= r2_j)."""
+    _em_dev(g, xn, yn, r2, hit)
+    rows, cols, ldg = _em_mat(g)
+    assert xn.dtype == yn.dtype == torch.float64 and xn.is_contiguous() and yn.is_contiguous() and xn.numel() == rows and yn.numel() == cols
+    assert r2.dtype == torch.float32 and r2.is_contiguous() and r2.numel() == cols
+    assert hit.dtype == torch.int32 and hit.is_contiguous() and hit.numel() == rows
+    L.check(L.load().dp_em_inside_ball(ops._p(g), rows, cols, ldg, ops._p(xn), ops._p(yn), ops._p(r2), ops._p(hit), ops._stream()),
+            'dp_em_inside_ball')
+    return hit
+
+
+def poly_sums(g, gamma, coef0, degree, out=None):
+    """float64 [2]: sum_ij (gamma g_ij + coef0)^degree and the same sum over i == j (meaningful on square blocks).  g: a Gram block
+    [rows, cols], or [S, rows, cols] partial Gram matrices over S slices of the feature dimension, which are added in double."""
+    _em_dev(g)
+    slabs, stride = (g.shape[0], g.stride(0)) if g.dim() == 3 else (1, 0)
+    rows, cols, ldg = _em_mat(g[0] if g.dim() == 3 else g)
+    out = out if out is not None else torch.empty(2, dtype=torch.float64, device=g.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 2
+    nb = max(1, min(rows, 1024))
+    part = torch.empty(2 * nb, dtype=torch.float64, device=g.device)
+    L.check(L.load().dp_em_poly_sums(ops._p(g), slabs, stride, rows, cols, ldg, float(gamma), float(coef0), int(degree), ops._p(part), nb,
+                                     ops._p(out), ops._stream()), 'dp_em_poly_sums')
+    return out
+
+
+def isc_rows(logits):
+    """Per row of fp32 logits [N, C], in float64: lse_i and h_i = sum_c p_ic (l_ic - lse_i)."""
+    _em_dev(logits)
+    n, c, ld = _em_mat(logits)
+    lse = torch.empty(n, dtype=torch.float64, device=logits.device)
+    h = torch.empty(n, dtype=torch.float64, device=logits.device)
+    L.check(L.load().dp_em_isc_rows(ops._p(logits), n, c, ld, ops._p(lse), ops._p(h), ops._stream()), 'dp_em_isc_rows')
+    return lse, h
+
+
+def isc_colmeans(logits, lse, lo, hi):
+    """q_c = mean over rows lo <= i < hi of exp(l_ic - lse_i), float64 [C]."""
+    _em_dev(logits, lse)
+    n, c, ld = _em_mat(logits)
+    assert 0 <= lo < hi <= n and lse.dtype == torch.float64 and lse.is_contiguous() and lse.numel() == n
+    q = torch.empty(c, dtype=torch.float64, device=logits.device)
+    L.check(L.load().dp_em_isc_colmeans(ops._p(logits), ld, ops._p(lse), lo, hi, c, ops._p(q), ops._stream()), 'dp_em_isc_colmeans')
+    return q
+
+
+class FeatureBank(FeatureStats):
+    """FeatureStats that also keeps the pool3 rows on the device: what IS, KID and precision / recall need beyond (mu, sigma).
+    Anything that fills a FeatureStats (get_activations, sample_to_dir, ldm_sampler.sample_classes, Sampler.sample_fid) fills it."""
+
+    def __init__(self, dims, device):
+        super().__init__(dims, device)
+        self.rows = []
+
+    def update(self, feats):
+        super().update(feats)
+        self.rows.append(feats.reshape(feats.shape[0], -1).to(torch.float32).clone())
+
+    def features(self):
+        """[N, dims] fp32 on the device, in the order the rows were seen."""
+        if len(self.rows) > 1:
+            self.rows = [torch.cat(self.rows)]
+        return self.rows[0] if self.rows else torch.empty((0, self.dims), dtype=torch.float32, device=self.s1.device)
+
+    def logits(self, inception):
+        """pool3 . fc.weight^T without the bias (torch_fidelity's "logits_unbiased"), [N, 1008] fp32."""
+        w = inception.inception.fc.weight.detach().to(torch.float32).contiguous()
+        return ops.linear_forward(self.features().contiguous(), w)
+
+
+def _feat(f):
+    _em_dev(f)
+    assert f.dim() == 2 and f.dtype == torch.float32, 'features are an fp32 [N, d] matrix'
+    return f.contiguous()
+
+
+def _em_blocks(nrows, ncols, d, row_block, col_block):
+    """Block sizes of a Gram pass: each operand block and the G block stay below the 2 GiB reach of dp_nt_gemm's 32-bit offsets."""
+    cap = (_GEMM_REACH - 1) // (4 * max(d, 1))
+    rb = max(1, min(int(row_block), nrows, cap))
+    cb = max(1, min(int(col_block), ncols, cap, (_GEMM_REACH - 1) // (4 * rb)))
+    assert rb * d * 4 < _GEMM_REACH and cb * d * 4 < _GEMM_REACH and rb * cb * 4 < _GEMM_REACH, (rb, cb, d)
+    return rb, cb
+
+
+def _gram_blocks(x, y, row_block, col_block):
+    """(r0, r1, c0, c1, G) over the blocks of x . y^T, G an [r1 - r0, c1 - c0] view of one reused buffer."""
+    rb, cb = _em_blocks(x.shape[0], y.shape[0], x.shape[1], row_block, col_block)
+    buf = torch.empty(rb * cb, dtype=torch.float32, device=x.device)
+    for r0 in range(0, x.shape[0], rb):
+        r1 = min(r0 + rb, x.shape[0])
+        for c0 in range(0, y.shape[0], cb):
+            c1 = min(c0 + cb, y.shape[0])
+            g = buf[:(r1 - r0) * (c1 - c0)].view(1, r1 - r0, c1 - c0)
+            ops.bmm_nt(x[r0:r1].unsqueeze(0), y[c0:c1].unsqueeze(0), out=g)
+            yield r0, r1, c0, c1, g[0]
+
+
+def knn_radii2(a, k, row_block=4096, col_block=65536):
+    """Squared radius of every row's k-neighbourhood within its own set: the (k + 1)-th smallest squared Euclidean distance from the
+    row to all rows of `a`, itself included.  fp32 [N]."""
+    a = _feat(a)
+    n = a.shape[0]
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError('prc_neighborhood %d outside 1 .. %d' % (k, KNN_MAX_K))
+    if n < k + 1:
+        raise ValueError('%d samples have no %d-th neighbour' % (n, k))
+    xn = row_norms2(a)
+    best = torch.empty((n, k + 1), dtype=torch.float32, device=a.device)
+    for r0, r1, c0, c1, g in _gram_blocks(a, a, row_block, col_block):
+        knn_merge(g, xn[r0:r1], xn[c0:c1], best[r0:r1], c0 == 0)
+    return best[:, k].contiguous()
+
+
+def inside_manifold(b, a, r2, row_block=4096, col_block=65536):
+    """int32 [Nb]: row i of `b` lies inside the ball of squared radius r2_j around some row j of `a`."""
+    b, a = _feat(b), _feat(a)
+    assert a.shape[1] == b.shape[1] and r2.numel() == a.shape[0]
+    bn, an = row_norms2(b), row_norms2(a)
+    r2 = r2.to(torch.float32).contiguous()
+    hit = torch.zeros(b.shape[0], dtype=torch.int32, device=b.device)
+    for r0, r1, c0, c1, g in _gram_blocks(b, a, row_block, col_block):
+        inside_ball(g, bn[r0:r1], an[c0:c1], r2[c0:c1], hit[r0:r1])
+    return hit
+
+
+def precision_recall(f1, f2, k=3, row_block=4096, col_block=65536):
+    """Kynkaanniemi et al. precision / recall as torch_fidelity's prc: precision = share of input1 (f1) inside input2's manifold,
+    recall = share of input2 inside input1's.  Four blocked N x N distance passes."""
+    r2_2 = knn_radii2(f2, k, row_block, col_block)
+    p = inside_manifold(f1, f2, r2_2, row_block, col_block)
+    r2_1 = knn_radii2(f1, k, row_block, col_block)
+    r = inside_manifold(f2, f1, r2_1, row_block, col_block)
+    precision = float(p.cpu().numpy().astype(np.float64).mean())
+    recall = float(r.cpu().numpy().astype(np.float64).mean())
+    f = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+    return {'precision': precision, 'recall': recall, 'f_score': float(f)}
+
+
+def kid_subset_indices(n1, n2, subsets, subset_size, rng_seed=2020):
+    """The index draws of KID: one RandomState, per subset choice(n1) then choice(n2), without replacement."""
+    if subset_size > n1 or subset_size > n2:
+        raise ValueError('kid_subset_size %d is larger than a sample set (%d, %d)' % (subset_size, n1, n2))
+    rng = np.random.RandomState(rng_seed)
+    return [(rng.choice(n1, subset_size, replace=False), rng.choice(n2, subset_size, replace=False)) for _ in range(subsets)]
+
+
+KID_SLAB = 128                      # feature columns per partial Gram matrix of kernel_inception_distance
+
+
+def _k_slabs(x, w):
+    """[m, d] -> [S, m, w]: the feature dimension cut into S = ceil(d / w) slices (the last one zero-padded), one matrix each."""
+    m, d = x.shape
+    s = -(-d // w)
+    if s == 1:
+        return x.unsqueeze(0)
+    if s * w != d:
+        x = torch.cat([x, torch.zeros((m, s * w - d), dtype=x.dtype, device=x.device)], 1)
+    return x.view(m, s, w).permute(1, 0, 2).contiguous()
+
+
+def kernel_inception_distance(f1, f2, subsets=100, subset_size=1000, degree=3, gamma=None, coef0=1, rng_seed=2020):
+    """Polynomial-kernel MMD^2 over random subsets (Binkowski et al.; torch_fidelity kid): mean and population std over subsets.
+    The reference forms K and mmd^2 in float64, and mmd^2 is a difference of nearly equal sums of cubes.  An fp32 product over all
+    2048 features is one fma chain whose error grows with its length; here each Gram matrix is S = ceil(d / KID_SLAB) batched fp32
+    products over 128-column slices of the features, added in double by the kernel that forms the cube and the sums."""
+    f1, f2 = _feat(f1), _feat(f2)
+    m, d = subset_size, f1.shape[1]
+    draws = kid_subset_indices(f1.shape[0], f2.shape[0], subsets, m, rng_seed)
+    gamma = 1.0 / d if gamma is None else gamma
+    w = min(d, KID_SLAB)
+    nslab = -(-d // w)
+    assert m * w * 4 < _GEMM_REACH and m * m * 4 < _GEMM_REACH, (m, d)
+    sums = torch.empty((subsets, 3, 2), dtype=torch.float64, device=f1.device)
+    g = torch.empty((nslab, m, m), dtype=torch.float32, device=f1.device)
+    for s, (i1, i2) in enumerate(draws):
+        x = _k_slabs(f1[torch.from_numpy(i1).to(f1.device)], w)
+        y = _k_slabs(f2[torch.from_numpy(i2).to(f2.device)], w)
+        for j, (u, v) in enumerate(((x, x), (y, y), (x, y))):
+            ops.bmm_nt(u, v, out=g)
+            poly_sums(g, gamma, coef0, degree, out=sums[s, j])
+    t = sums.cpu().numpy()
+    if m > 1:
+        mmd = (t[:, 0, 0] - t[:, 0, 1] + t[:, 1, 0] - t[:, 1, 1]) / (m * (m - 1)) - 2 * t[:, 2, 0] / (m * m)
+    else:
+        mmd = np.full(subsets, np.nan)
+    return {'kernel_inception_distance_mean': float(np.mean(mmd)), 'kernel_inception_distance_std': float(np.std(mmd))}
+
+
+def inception_score(logits, splits=10, shuffle=True, rng_seed=2020):
+    """exp(mean_i KL(p_i || q)) per split of the (permuted) rows, q the split's mean p; mean and population std over the splits.
+    Per split, mean_i sum_c p (log p - log q) = mean_i h_i - sum_c q_c log q_c with h_i = sum_c p_ic log p_ic."""
+    _em_dev(logits)
+    assert logits.dim() == 2 and logits.dtype == torch.float32
+    n = logits.shape[0]
+    if shuffle:
+        perm = np.random.RandomState(rng_seed).permutation(n)
+        logits = logits[torch.from_numpy(perm).to(logits.device)]
+    logits = logits.contiguous()
+    lse, h = isc_rows(logits)
+    if n < splits:
+        raise ValueError('%d rows cannot fill %d splits' % (n, splits))
+    bounds = [(i * n // splits, (i + 1) * n // splits) for i in range(splits)]
+    qs = torch.stack([isc_colmeans(logits, lse, lo, hi) for lo, hi in bounds]).cpu().numpy()
+    h = h.cpu().numpy()
+    scores = []
+    for (lo, hi), q in zip(bounds, qs):
+        qlq = np.sum(np.where(q > 0, q * np.log(np.where(q > 0, q, 1.0)), 0.0))       # 0 log 0 = 0
+        scores.append(np.exp(np.mean(h[lo:hi]) - qlq))
+    return {'inception_score_mean': float(np.mean(scores)), 'inception_score_std': float(np.std(scores))}
+
+
+def _bank_of(inp, model, batch_size, device, samples_find_deep):
+    if isinstance(inp, FeatureBank):
+        return inp
+    if not os.path.isdir(str(inp)):
+        raise RuntimeError('Invalid path: %s' % inp)
+    path = pathlib.Path(inp)
+    pat = '**/*.{}' if samples_find_deep else '*.{}'
+    files = sorted([file for ext in IMAGE_EXTENSIONS for file in path.glob(pat.format(ext))])
+    bank = FeatureBank(2048, torch.device(device))
+    return get_activations(_image_batches(files, batch_size, device), model, batch_size, 2048, device, stats=bank)
+
+
+def calculate_metrics(input1, input2=None, isc=True, fid=True, kid=True, prc=True, samples_find_deep=True, model=None, batch_size=50,
+                      device='cuda', isc_splits=10, kid_subsets=100, kid_subset_size=1000, kid_degree=3, kid_gamma=None, kid_coef0=1,
+                      prc_neighborhood=3, rng_seed=2020, verbose=False):
+    """ldm_exp/test_diffusion.py's torch_fidelity.calculate_metrics(input1, input2, isc, fid, kid, prc, samples_find_deep) on the
+    engine: input1 (the evaluated set) and input2 (the reference set) are folders of images or FeatureBanks; returns a dict under
+    torch_fidelity's key names.  One device; `model` is an InceptionV3 (pool3) -- needed for folders and for isc."""
+    if torch.device(device).type != 'cuda':
+        raise RuntimeError('calculate_metrics runs on the MI355X HIP kernels only (no CPU / PyTorch fallback)')
+    if (fid or kid or prc) and input2 is None:
+        raise ValueError('fid, kid and prc compare two inputs')
+    banked = isinstance(input1, FeatureBank) and (input2 is None or isinstance(input2, FeatureBank))
+    if model is None and (isc or not banked):
+        model = InceptionV3([InceptionV3.DEFAULT_BLOCK_INDEX]).to(device)
+    b1 = _bank_of(input1, model, batch_size, device, samples_find_deep)
+    b2 = _bank_of(input2, model, batch_size, device, samples_find_deep) if input2 is not None else None
+    out = {}
+    if isc:
+        out.update(inception_score(b1.logits(model), isc_splits, True, rng_seed))
+    if fid:
+        m1, s1 = b1.finalize()
+        m2, s2 = b2.finalize()
+        out['frechet_inception_distance'] = float(calculate_frechet_distance(m1, s1, m2, s2))
+    if kid:
+        out.update(kernel_inception_distance(b1.features(), b2.features(), kid_subsets, kid_subset_size, kid_degree, kid_gamma,
+                                             kid_coef0, rng_seed))
+    if prc:
+        out.update(precision_recall(b1.features(), b2.features(), prc_neighborhood))
+    if verbose:
+        for k_, v in out.items():
+            print('%s: %s' % (k_, v))
+    return out

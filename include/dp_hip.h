@@ -518,6 +518,34 @@ int dp_ssim(const float* x, const float* y, int N, int C, int H, int W, float da
 long long dp_ssim_workspace(int N, int C, int H, int W);
 int dp_mse_per_image(const float* a, const float* b, int N, long long per, float* out, void* stream);
 
+/* ---- Inception Score / KID / precision-recall reductions (csrc/evalmetrics.hip; metrics.py calculate_metrics restates the
+ * reference's ldm_exp/test_diffusion.py, a torch_fidelity.calculate_metrics call).  G is a block of a Gram matrix X . Y^T written by
+ * dp_nt_gemm: `rows` x `cols` fp32 with row stride ldg floats (any alignment: 16-byte loads between a scalar head and tail per row).
+ * Squared distances are d2_ij = max(xn_i + yn_j - 2 G_ij, 0), formed in double from the double norms of dp_em_row_norms2 and
+ * rounded to fp32.  No atomics; every sum has a fixed order (two calls give the same bits).
+ * dp_em_row_norms2: out[i] = sum_c x[i * ld + c]^2 in double.
+ * dp_em_knn_merge: best [rows][k] fp32, ascending: replaced by the k smallest of its old contents (ignored when first != 0) and
+ *   the block's d2_i*.  Fewer than k values so far leave +inf at the end.  1 <= k <= DP_EM_MAX_K, else hipErrorNotSupported.
+ * dp_em_inside_ball: hit[i] |= any_j (d2_ij <= r2[j]); hit is int32 [rows], 0 / 1, initialised by the caller.
+ * dp_em_poly_sums: out[0] = sum_ij (gamma g_ij + coef0)^degree and out[1] = the same over i == j, in double, where
+ *   g_ij = sum_s G[s * slab_stride + i * ldg + j] over `slabs` partial Gram matrices (products over slices of the feature
+ *   dimension), added in double in slab order; part is a workspace of 2 * nblocks doubles (nblocks workgroups take the rows
+ *   round-robin, 1 <= nblocks <= 65536, degree >= 1).
+ * dp_em_isc_rows: per row of the fp32 logits [n][c] (row stride ld), in double: lse[i] = log sum_c exp(l_ic) and
+ *   h[i] = sum_c p_ic (l_ic - lse[i]), p = softmax.
+ * dp_em_isc_colmeans: q[c] = mean over rows lo <= i < hi of exp(l_ic - lse[i]), in double. */
+#define DP_EM_MAX_K 9
+int dp_em_row_norms2(const float* x, long long n, int d, long long ld, double* out, void* stream);
+int dp_em_knn_merge(const float* G, long long rows, long long cols, long long ldg, const double* xn, const double* yn, int k,
+                    int first, float* best, void* stream);
+int dp_em_inside_ball(const float* G, long long rows, long long cols, long long ldg, const double* xn, const double* yn,
+                      const float* r2, int* hit, void* stream);
+int dp_em_poly_sums(const float* G, int slabs, long long slab_stride, long long rows, long long cols, long long ldg, double gamma,
+                    double coef0, int degree, double* part, int nblocks, double* out, void* stream);
+int dp_em_isc_rows(const float* logits, long long n, int c, long long ld, double* lse, double* h, void* stream);
+int dp_em_isc_colmeans(const float* logits, long long ld, const double* lse, long long lo, long long hi, int c, double* q,
+                       void* stream);
+
 /* Input pipeline (utils.py:8-58 get_dataset transforms; ddpm_exp/datasets/__init__.py:176-192 data_transform): decoded
  * uint8 images -> fp32 NCHW batch: x/255 (ToTensor), horizontal flip of image n with probability flip_thr24 / 2^24
  * (RandomHorizontalFlip; Philox decision on counter (n_off + n, 0, rng.site, rng.step), key rng.seed), mode 1:
