@@ -69,6 +69,10 @@ class SliceItem(C.Structure):
                 ('n_keep', C.c_int), ('blk0', C.c_int), ('nblk', C.c_int), ('_pad', C.c_int), ('keep_off', LL)]
 
 
+class ScoreEntry(C.Structure):
+    _fields_ = [('m', ScoreMember), ('score_off', LL), ('n0', C.c_int), ('_pad', C.c_int)]
+
+
 class PackItem(C.Structure):
     _fields_ = [('W', C.c_void_p), ('dst', C.c_void_p), ('Co', C.c_int), ('Ci', C.c_int), ('taps', C.c_int), ('mode', C.c_int),
                 ('ld', C.c_int), ('blk0', C.c_int), ('nblk', C.c_int), ('_pad', C.c_int)]
@@ -158,6 +162,9 @@ SIGNATURES = {
     'dp_gather_add': [_vp, _vp, _i, _vp, _vp],
     'dp_group_score': [C.POINTER(ScoreMember), _i, _i, _vp, _vp, _vp, _vp],
     'dp_slice_batch': [C.POINTER(SliceItem), _i, _vp, _vp],
+    'dp_score_groups': [C.POINTER(ScoreEntry), _i, _vp, _vp, _ll, _vp, _ll, _vp, _ll, _vp],
+    'dp_select_smallest_workspace': [_ll, _i],
+    'dp_select_smallest': [_vp, _ll, C.POINTER(LL), _i, _ll, _vp, _ll, _vp, _vp, _vp],
     'dp_sumsq_partials': [_vp, _ll, _vp, _i, _vp],
     'dp_clip_coef': [_vp, _i, _f, _vp, _vp, _vp],
     'dp_adam_ema': [_vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _f, _f, _f, _vp],
@@ -223,7 +230,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = C.c_longlong if name in ('dp_launch_count', 'dp_ssim_workspace') else C.c_int
+        fn.restype = C.c_longlong if name in ('dp_launch_count', 'dp_ssim_workspace', 'dp_select_smallest_workspace') else C.c_int
     _lib = lib
     return lib
 

@@ -484,3 +484,26 @@ def encode_first_stage(vq, images, scale_factor=1.0):
     if scale_factor != 1.0:
         z = ops.axpby(z.contiguous(), float(scale_factor), torch.empty_like(z), 0.0)      # `self.scale_factor * z` in fp32
     return z
+
+
+def prune_ldm_model(model, pruning_ratio=0.3, importance=None, global_pruning=False, iterative_steps=1, round_to=2):
+    """prune_ldm.py:70-100 after the importance pass: the pruner with the attention heads of every CrossAttention as
+    `channel_groups` for its to_q / to_k / to_v, `round_to=2` and the output head ignored; every yielded group is pruned.
+    global_pruning: one ranking across every group of the network (metapruner.py:256-297) instead of the ratio per layer.
+    Returns the pruner (`.records`, `.pruning_history()`)."""
+    from . import ldm, pruning
+    channel_groups = {}
+    for m in model.modules():
+        if isinstance(m, ldm.CrossAttention):
+            channel_groups[m.to_q] = channel_groups[m.to_k] = channel_groups[m.to_v] = m.heads
+    imp = importance if importance is not None else pruning.TaylorImportance()
+    pr = pruning.MagnitudePruner(model, None, importance=imp, global_pruning=global_pruning, iterative_steps=iterative_steps,
+                                 channel_groups=channel_groups, ch_sparsity=pruning_ratio, ignored_layers=[model.out],
+                                 round_to=round_to)
+    for _ in range(iterative_steps):
+        for g in pr.step(interactive=True):
+            g.prune()
+    pruning.fix_static_attributes(model)
+    if getattr(model, '_engine', None) is not None:
+        model._engine.packs.clear()
+    return pr

@@ -1686,6 +1686,66 @@ def slice_batch(items, keep_dev):
     L.check(_lib().dp_slice_batch(arr, n, _p(keep_dev), _stream()), 'dp_slice_batch')
 
 
+def score_groups(groups, idx_dev, scratch, scores):
+    """The scores of ALL groups in one launch pair (include/dp_hip.h dp_score_groups).  groups: list of (members, n0), members as
+    for group_score (offsets into the shared `scratch` / `idx_dev`); group i's scores land at scores[sum of the earlier n0 ...].
+    The member table is copied to the device by the launcher and read from there."""
+    n = sum(len(members) for members, _ in groups)
+    total = sum(n0 for _, n0 in groups)
+    assert scores.is_cuda and scores.dtype == _f32 and scores.is_contiguous() and scores.numel() == total and scratch.is_cuda, \
+        'score_groups takes device tensors (no CPU path)'
+    assert idx_dev is None or (idx_dev.is_cuda and idx_dev.dtype == torch.int64 and idx_dev.is_contiguous())
+    arr = (L.ScoreEntry * max(n, 1))()
+    i = off = 0
+    for members, n0 in groups:
+        assert members and n0 > 0, 'a group without members has no score'
+        for m in members:
+            w, g = m['w'], m['g']
+            assert w.is_cuda and g.is_cuda and w.is_contiguous() and g.is_contiguous() and w.dtype == g.dtype == _f32
+            assert w.numel() == g.numel() == m['R'] * m['C'] * m['T'], 'member view does not cover its tensors'
+            a = arr[i].m
+            a.w, a.g = w.data_ptr(), g.data_ptr()
+            a.R, a.C, a.T, a.dim, a.mode = m['R'], m['C'], m['T'], m['dim'], m['mode']
+            a.full_off, a.col_off, a.idx_off = m['full_off'], m['col_off'], m['idx_off']
+            arr[i].score_off, arr[i].n0 = off, n0
+            i += 1
+        off += n0
+    table = torch.empty(max(n, 1) * C.sizeof(L.ScoreEntry), dtype=torch.uint8, device=scores.device)
+    L.check(_lib().dp_score_groups(arr, n, _p(table), _p(idx_dev), 0 if idx_dev is None else idx_dev.numel(), _p(scratch),
+                                   scratch.numel(), _p(scores), total, _stream()), 'dp_score_groups')
+    scores._dp_table = (arr, table)           # the host table outlives the asynchronous copy, the device one the kernels
+    return scores
+
+
+def select_smallest(scores, offsets, k, raw=False):
+    """k-th smallest of the concatenated fp32 `scores` (device) and, per group (offsets: ascending host ints, [0] = 0, [-1] = n),
+    the ascending positions with score <= that threshold, compacted on the device and fetched in ONE copy (dp_select_smallest).
+    Returns (threshold as a Python float, [int64 numpy index array per group]); raw=True adds the fetched int32 buffer itself
+    (its layout: include/dp_hip.h).  A NaN score raises RuntimeError."""
+    import numpy as np
+    n, G = scores.numel(), len(offsets) - 1
+    assert scores.is_cuda and scores.dtype == _f32 and scores.is_contiguous(), 'select_smallest takes a device tensor (no CPU path)'
+    if not (G >= 1 and offsets[0] == 0 and offsets[-1] == n and 1 <= k <= n and all(a < b for a, b in zip(offsets, offsets[1:]))):
+        raise ValueError('select_smallest: offsets must cover the %d scores and 1 <= k <= n (k = %d)' % (n, k))
+    lib = _lib()
+    off = (L.LL * (G + 1))(*[int(o) for o in offsets])
+    wb = int(lib.dp_select_smallest_workspace(n, G))
+    work = torch.empty(wb, dtype=torch.uint8, device=scores.device)
+    out_dev = torch.empty(2 + G + n, dtype=torch.int32, device=scores.device)
+    out = torch.empty(2 + G + n, dtype=torch.int32)
+    try:
+        L.check(lib.dp_select_smallest(_p(scores), n, off, G, int(k), _p(work), wb, _p(out_dev), _p(out), _stream()),
+                'dp_select_smallest')
+    except L.DpHipError as e:
+        if e.code == 1:                       # hipErrorInvalidValue with arguments that passed the checks above: a NaN score
+            raise RuntimeError('select_smallest: the scores contain NaN (no k-th smallest exists)') from e
+        raise
+    o = out.numpy()
+    thres = float(o[:1].view(np.float32)[0])
+    idx = [o[2 + G + offsets[g]:2 + G + offsets[g] + int(o[2 + g])].astype(np.int64) for g in range(G)]
+    return (thres, idx, out) if raw else (thres, idx)
+
+
 def gather_add(src, idx_long, dst):
     """dst[i] += src[idx[i]]"""
     assert idx_long.dtype == torch.int64 and idx_long.numel() == dst.numel()

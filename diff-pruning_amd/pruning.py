@@ -3,10 +3,12 @@
 Mirrors the part of (vendored) torch_pruning the reference's prune scripts use:
   importance.TaylorImportance / MagnitudeImportance / RandomImportance   importance.py:11-16,59-126,221-225,332-434
   pruner.MagnitudePruner (= MetaPruner).step(interactive) / prune_local  pruner/algorithms/metapruner.py:11-254
+  MetaPruner(global_pruning=True) / prune_global                         pruner/algorithms/metapruner.py:126-133,256-297
   Group.prune()                                                          dependency.py:157-185
   function.prune_{conv,linear}_{out,in}_channels, prune_groupnorm_out_channels   pruner/function.py:85-146,168-207,274-302
 Scores are computed on the device by the fused |w*g| channel-reduction kernel (csrc/importance.hip); the
-argsort over the <= 1024 scores of a group and the channel slicing itself are host/plumbing work.
+argsort over the <= 1024 scores of a group and the channel slicing itself are host/plumbing work.  Global pruning scores every
+group in one launch pair and selects on the device (csrc/prune_global.hip).
 
 `TaylorImportance.__call__(group, ch_groups=1)` accepts both this module's groups and groups produced by a real
 `torch_pruning.DependencyGraph` (items `(dep, idxs)` with `dep.target.module` / `dep.handler`), so it can be handed
@@ -408,6 +410,70 @@ class Importance(abc.ABC):
     def __call__(self, group):
         raise NotImplementedError
 
+    def score_all(self, groups, ch_groups=None):
+        """Global pruning (metapruner.py:259-267): the score of EVERY group on the weights as they are now, one entry per group
+        (None where the criterion has no term).  This form calls the criterion group by group."""
+        chg = ch_groups if ch_groups is not None else [1] * len(groups)
+        return [self(g, ch_groups=c) for g, c in zip(groups, chg)]
+
+
+def _score_all_batched(crit, groups):
+    """Every group's member reductions and member sums in ONE launch pair (ops.score_groups, csrc/prune_global.hip): the member
+    descriptors of `_score_batched`, with offsets into one scratch / index / score vector shared by all groups -- the same
+    per-member reductions in the same member order as the criterion's `__call__`, hence the same bits -- then the criterion's own
+    per-group finish (`_finish`: group_reduction / normalizer / |.|).  `crit` supplies `_terms(group)` -> [(layer, kind, idxs)],
+    `_desc(layer, kind)` -> (w, g, R, C, T, dim, mode).  Returns the list of per-group scores, or None (not applicable: the
+    caller scores group by group)."""
+    if not PRUNE_BATCH or not hasattr(ops, 'score_groups') or not getattr(crit, '_batchable', True):
+        return None
+    per_group, idx_host, need, dev = [], [], 0, None
+    for group in groups:
+        terms = crit._terms(group)
+        if not terms:
+            per_group.append(None)
+            continue
+        n0 = len(terms[0][2])
+        members = []
+        for layer, kind, idxs in terms:
+            if len(idxs) != n0:             # importance.py:422-426: mis-sized members are dropped
+                continue
+            w, g, R, Cc, T, dim, mode = crit._desc(layer, kind)
+            dev = w.device if dev is None else dev
+            if not (w.is_contiguous() and g.is_contiguous()) or w.device != dev or g.device != dev:
+                return None
+            cols = mode != 3 and dim == 1
+            n_full = Cc if cols else R
+            m = dict(w=w, g=g, R=R, C=Cc, T=T, dim=dim, mode=mode, full_off=0, col_off=0, idx_off=-1)
+            if cols:
+                m['col_off'] = need
+                need += Cc * T
+            else:
+                m['full_off'] = need
+                need += n_full
+            if not (n_full == n0 and idxs[0] == 0 and idxs[-1] == n0 - 1):
+                if idxs[0] < 0 or idxs[-1] >= n_full:
+                    raise IndexError('group member index outside its layer (%d channels)' % n_full)
+                m['idx_off'] = len(idx_host)
+                idx_host.extend(idxs)
+            members.append(m)
+        per_group.append((members, n0))
+    live = [pg for pg in per_group if pg is not None]
+    if not live:
+        return [None] * len(groups)
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    idx_dev = torch.from_numpy(np.asarray(idx_host, dtype=np.int64)).to(dev) if idx_host else None
+    scores = torch.empty(sum(n0 for _, n0 in live), dtype=torch.float32, device=dev)
+    ops.score_groups(live, idx_dev, scratch, scores)
+    out, off = [], 0
+    for pg in per_group:
+        if pg is None:
+            out.append(None)
+            continue
+        members, n0 = pg
+        out.append(crit._finish(scores[off:off + n0], len(members)))
+        off += n0
+    return out
+
 
 _MODES = {'sum_sq': 0, 'sum_abs': 1, 'abs_sum': 2}
 _NO_TERM = ('ln', 'bn', 'inorm', 'prelu', 'embed')                     # member kinds the vendored criteria have no branch for
@@ -505,6 +571,50 @@ class TaylorImportance(Importance):
         ops.group_score(members, n0, idx_dev, self._scratch, score)
         return score, len(members)
 
+    def _terms(self, group):
+        """The members that carry a term, as `__call__` selects them."""
+        terms = []
+        for dep, idxs in group:
+            idxs.sort()
+            kind = _member_kind(dep)
+            if kind is None or kind in _NO_TERM:
+                continue
+            layer = dep.target.module
+            if kind == 'gn' and (not layer.affine or not self.groupnorm_term):
+                continue
+            terms.append((layer, kind, idxs))
+        return terms
+
+    def _desc(self, layer, kind):
+        w, g = layer.weight.data, layer.weight.grad
+        if g is None:
+            raise RuntimeError('TaylorImportance needs accumulated gradients (run the sweep before pruner.step())')
+        g = g.data
+        if kind == 'gn':
+            return w, g, w.shape[0], 1, 1, 0, 3
+        dim = 0 if kind == 'out' else 1
+        if getattr(layer, 'transposed', False):
+            dim = 1 - dim
+        T = 1
+        for v in w.shape[2:]:
+            T *= v
+        return w, g, w.shape[0], w.shape[1] if w.dim() > 1 else 1, T, dim, _MODES[self.mode]
+
+    def _finish(self, score, used):
+        if self.multivariable is not None:
+            score = score.clone()               # a tensor of its own, as `__call__` normalises one
+            if self.group_reduction == 'mean':
+                ops.axpby(score, 0.0, score, 1.0 / used)
+            if self.normalizer == 'mean':
+                mean = float(score.mean())
+                ops.axpby(score, 0.0, score, 1.0 / mean)
+        return score
+
+    @torch.no_grad()
+    def score_all(self, groups, ch_groups=None):
+        got = _score_all_batched(self, groups)
+        return got if got is not None else super().score_all(groups, ch_groups)
+
     @torch.no_grad()
     def __call__(self, group, ch_groups=1):
         terms = []
@@ -574,6 +684,53 @@ class _GradCriterion(Importance):
         for i, m in enumerate(modes):
             ops.wg_reduce(w.contiguous(), g.contiguous(), dim, m, full, i > 0, self._scratch)
         return full, n_full
+
+    @property
+    def _batchable(self):
+        """One reduction per member: a member that accumulates two modes (FullTaylorImportance(order=2)) adds them BEFORE the
+        member sum, which the one-pass table cannot express bit for bit -> scored group by group."""
+        return len(self.conv_modes) == 1 and len(self.gn_modes) <= 1
+
+    def _terms(self, group):
+        terms = []
+        for dep, idxs in group:
+            idxs.sort()
+            kind = _member_kind(dep)
+            if kind is None or kind in _NO_TERM:
+                continue
+            layer = dep.target.module
+            if kind == 'gn' and (not layer.affine or not self.gn_modes):
+                continue
+            terms.append((layer, kind, idxs))
+        return terms
+
+    def _desc(self, layer, kind):
+        w, g = layer.weight.data, layer.weight.grad
+        if g is None:
+            raise RuntimeError('%s needs accumulated gradients (run the sweep before pruner.step())' % type(self).__name__)
+        g = g.data
+        if kind == 'gn':                        # `_member_score`: the [n, 1] view through the row reduction
+            return w, g, w.shape[0], 1, 1, 0, self.gn_modes[0]
+        dim = 0 if kind == 'out' else 1
+        if getattr(layer, 'transposed', False):
+            dim = 1 - dim
+        T = 1
+        for v in w.shape[2:]:
+            T *= v
+        return w, g, w.shape[0], w.shape[1] if w.dim() > 1 else 1, T, dim, self.conv_modes[0]
+
+    def _finish(self, score, used):
+        self._used = used
+        if self.final_abs:
+            out = torch.empty_like(score)
+            ops.wg_reduce(score.view(-1, 1), torch.ones_like(score).view(-1, 1), 0, _F_SIGNED, out, False)
+            score = out
+        return score
+
+    @torch.no_grad()
+    def score_all(self, groups, ch_groups=None):
+        got = _score_all_batched(self, groups)
+        return got if got is not None else super().score_all(groups, ch_groups)
 
     @torch.no_grad()
     def __call__(self, group, ch_groups=1):
@@ -660,6 +817,21 @@ class MagnitudeImportance(_GradCriterion):
                 self._scratch = torch.empty(max(need, 1 << 16), dtype=torch.float32, device=w.device)
         ops.wg_reduce(w, w, dim, _F_ABS, full, False, self._scratch)          # |w*w| = |w|^2
         return full, n_full
+
+    def _desc(self, layer, kind):
+        w = layer.weight.data
+        T = 1
+        for v in w.shape[2:]:
+            T *= v
+        return w, w, w.shape[0], w.shape[1] if w.dim() > 1 else 1, T, 0 if kind == 'out' else 1, _F_ABS
+
+    def _finish(self, score, used):
+        score = super()._finish(score, used).clone()
+        if self.group_reduction == 'mean':
+            ops.axpby(score, 0.0, score, 1.0 / used)
+        if self.normalizer == 'mean':
+            ops.axpby(score, 0.0, score, 1.0 / float(score.mean()))
+        return score
 
     @torch.no_grad()
     def __call__(self, group, ch_groups=1):
@@ -768,15 +940,14 @@ class DependencyGraph:
 
 
 class MetaPruner:
-    """metapruner.py:11-254 (local pruning path used by the reference; `global_pruning` is not on the hot path)."""
+    """metapruner.py:11-297: the local pruning path the reference's scripts use (`prune_local`) and, with
+    `global_pruning=True`, one ranking across every group of the network (`prune_global`)."""
 
     def __init__(self, model, example_inputs=None, importance=None, global_pruning=False, ch_sparsity=0.5,
                  ch_sparsity_dict=None, max_ch_sparsity=1.0, iterative_steps=1,
                  iterative_sparsity_scheduler=linear_scheduler, ignored_layers=None, channel_groups=None, round_to=None,
                  root_module_types=(nn.Conv2d, nn.Linear)):
-        if global_pruning:
-            raise NotImplementedError('global pruning is not used by the reference prune scripts')
-        self.model, self.importance = model, importance
+        self.model, self.importance, self.global_pruning = model, importance, bool(global_pruning)
         self.ch_sparsity, self.max_ch_sparsity = ch_sparsity, max_ch_sparsity
         self.round_to, self.root_module_types = round_to, root_module_types
         self.channel_groups = dict(channel_groups) if channel_groups else {}
@@ -801,6 +972,11 @@ class MetaPruner:
             if isinstance(m, nn.GroupNorm):
                 self.channel_groups[m] = m.num_groups
         self.records = []          # per pruned group: (root name, ch_groups, score tensor, pruned idxs) for reporting
+        self.global_threshold = None
+        if self.global_pruning:                         # metapruner.py:126-133
+            self.initial_total_channels = 0
+            for group in self.DG.get_all_groups(self.ignored_layers, self.root_module_types):
+                self.initial_total_channels += _out_channels(group[0][0].target.module) // self.get_channel_groups(group)
 
     def get_target_sparsity(self, layer):
         return self.ch_sparsity_dict.get(layer, self.per_step_ch_sparsity)[self.current_step]
@@ -810,6 +986,12 @@ class MetaPruner:
 
     def step(self, interactive=False):
         self.current_step += 1
+        if self.global_pruning:
+            if interactive:
+                return self.prune_global()
+            for group in self.prune_global():
+                group.prune()
+            return
         if interactive:
             return self.prune_local()
         for group in self.prune_local():
@@ -877,6 +1059,64 @@ class MetaPruner:
             pg = self.DG.get_pruning_group(module, fn, idxs)
             if self.DG.check_pruning_group(pg):
                 self.records.append((group[0][0].target.name, ch_groups, imp_host, sorted(idxs)))
+                yield pg
+
+    def prune_global(self):
+        """metapruner.py:256-297, quirks included: every group is scored on the UNPRUNED weights (of a head / GroupNorm-grouped
+        root only the first sub-group's scores are ranked), the kept scores are concatenated in group order, the threshold is the
+        n_pruned-th smallest of them, and each group loses the channels whose score is <= the threshold (ties at the threshold all
+        go; a group may lose none, and is still yielded).  Scores: one launch pair for all groups (`importance.score_all`); the
+        selection and the per-group index lists: `ops.select_smallest`, one device-to-host copy.  Without the batched kernels
+        (DP_NO_PRUNE_BATCH, a criterion that cannot batch, host tensors) the same arithmetic runs group by group / through
+        torch.topk.  `records` rows hold the RANKED scores (the first sub-group's for a grouped root)."""
+        if self.current_step > self.iterative_steps:
+            return
+        groups, chg = [], []
+        for group in self.DG.get_all_groups(self.ignored_layers, self.root_module_types):
+            if self._check_sparsity(group):
+                groups.append(group)
+                chg.append(self.get_channel_groups(group))
+        if PRUNE_BATCH and hasattr(self.importance, 'score_all'):
+            imps = self.importance.score_all(groups, chg)
+        else:
+            imps = [self.estimate_importance(g, ch_groups=c) for g, c in zip(groups, chg)]
+        ranked = []
+        for group, ch_groups, imp in zip(groups, chg, imps):
+            if imp is None:
+                continue
+            if ch_groups > 1:
+                imp = imp[:len(imp) // ch_groups]
+            ranked.append((group, ch_groups, imp))
+        if not ranked:
+            return
+        imp = torch.cat([r[-1] for r in ranked], dim=0)
+        n_pruned = len(imp) - int(self.initial_total_channels * (1 - self.per_step_ch_sparsity[self.current_step]))
+        if n_pruned <= 0:
+            return
+        offsets = [0]
+        for r in ranked:
+            offsets.append(offsets[-1] + len(r[-1]))
+        imp_host = imp.detach().float().cpu()
+        on_device = imp.is_cuda or getattr(ops, 'IS_MOCK', False)
+        if PRUNE_BATCH and hasattr(ops, 'select_smallest') and on_device and all(a < b for a, b in zip(offsets, offsets[1:])):
+            thres, picked = ops.select_smallest(imp.detach().float().contiguous(), offsets, n_pruned)
+        else:
+            topk_imp, _ = torch.topk(imp_host, k=n_pruned, largest=False)
+            thres = float(topk_imp[-1])
+            picked = [(imp_host[a:b] <= topk_imp[-1]).nonzero().view(-1).numpy() for a, b in zip(offsets, offsets[1:])]
+        self.global_threshold = thres
+        for (group, ch_groups, _), idxs, a, b in zip(ranked, picked, offsets, offsets[1:]):
+            module = group[0][0].target.module
+            fn = group[0][0].handler
+            idxs = [int(i) for i in idxs]
+            if ch_groups > 1:
+                gs = _out_channels(module) // ch_groups
+                idxs = [i + gs * c for c in range(ch_groups) for i in idxs]
+            if self.round_to:
+                idxs = idxs[:len(idxs) - (len(idxs) % self.round_to)]
+            pg = self.DG.get_pruning_group(module, fn, idxs)
+            if self.DG.check_pruning_group(pg):
+                self.records.append((group[0][0].target.name, ch_groups, imp_host[a:b], sorted(idxs)))
                 yield pg
 
 

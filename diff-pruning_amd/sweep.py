@@ -520,16 +520,20 @@ def taylor_sweep(model, scheduler, clean_images, noise, num_steps=1000, thr=None
     return dict(losses=losses, steps=steps, global_batch=B_global)
 
 
-def prune_model(model, pruning_ratio=0.3, importance=None, ignored_layers=None, channel_groups=None):
+def prune_model(model, pruning_ratio=0.3, importance=None, ignored_layers=None, channel_groups=None, global_pruning=False,
+                iterative_steps=1):
     """ddpm_prune.py:79-116: build the pruner, run `pruner.step(interactive=True)` pruning every yielded group,
-    then fix the static `channels` attributes.  Returns the pruner (its `.records` hold scores and masks)."""
+    then fix the static `channels` attributes.  Returns the pruner (its `.records` hold scores and masks).
+    global_pruning: one ranking across every group (metapruner.py:256-297) instead of `pruning_ratio` per layer;
+    iterative_steps: that many `step()`s over the gradients already accumulated (linear sparsity schedule)."""
     from . import pruning
     imp = importance if importance is not None else pruning.TaylorImportance()
-    pr = pruning.MagnitudePruner(model, None, importance=imp, iterative_steps=1, channel_groups=channel_groups or {},
-                                 ch_sparsity=pruning_ratio,
+    pr = pruning.MagnitudePruner(model, None, importance=imp, global_pruning=global_pruning, iterative_steps=iterative_steps,
+                                 channel_groups=channel_groups or {}, ch_sparsity=pruning_ratio,
                                  ignored_layers=ignored_layers if ignored_layers is not None else [model.conv_out])
-    for g in pr.step(interactive=True):
-        g.prune()
+    for _ in range(iterative_steps):
+        for g in pr.step(interactive=True):
+            g.prune()
     pruning.fix_static_attributes(model)
     if getattr(model, '_engine', None) is not None:
         model._engine.packs.clear()

@@ -398,6 +398,29 @@ typedef struct dp_slice_item {
 } dp_slice_item;
 int dp_slice_batch(const dp_slice_item* items, int n, const int64_t* keep, void* stream);
 
+/* Global pruning (metapruner.py:256-297; csrc/prune_global.hip): every group scored on the unpruned weights, one threshold.
+ * dp_score_groups = dp_group_score for ALL groups in one launch pair.  `entries` (host, n of them) is the member table: the
+ * members of a group are adjacent, in dp_group_score's member order, and share score_off (the group's offset into the
+ * concatenated score vector) and n0; the groups tile scores[0 .. n_scores) in table order.  The launcher checks every offset
+ * against idx_len / scratch_len / n_scores, fills m.blk0 and copies the table to table_dev (device, n entries), from where the
+ * kernels read it.  scores[score_off + j] has the bits dp_group_score gives score[j] for that group.
+ * dp_select_smallest: thres = the k-th smallest (1 <= k <= n) of scores[0 .. n), exactly; -0.0 counts as +0.0 (a zero threshold
+ * is returned as +0.0).  group_off (host, groups + 1 ascending offsets, [0] = 0, [groups] = n) cuts the vector into groups.
+ * out_dev / out_host: 2 + groups + n ints -- [0] the threshold's bits, [1] the NaN count, [2 + g] the number of positions of
+ * group g with score <= thres, [2 + groups + group_off[g] + j] the j-th of them (ascending, relative to the group; the rest of
+ * the group's region is 0).  The call copies out_dev to out_host and waits for the stream; any NaN -> hipErrorInvalidValue.
+ * `work`: dp_select_smallest_workspace(n, groups) bytes of device memory. */
+typedef struct dp_score_entry {
+    dp_score_member m;
+    long long score_off;
+    int n0, _pad;
+} dp_score_entry;
+int dp_score_groups(dp_score_entry* entries, int n, dp_score_entry* table_dev, const int64_t* idx, long long idx_len,
+                    float* scratch, long long scratch_len, float* scores, long long n_scores, void* stream);
+long long dp_select_smallest_workspace(long long n, int groups);
+int dp_select_smallest(const float* scores, long long n, const long long* group_off, int groups, long long k, void* work,
+                       long long work_bytes, int* out_dev, int* out_host, void* stream);
+
 /* Fused finetune update over flat buffers (ddpm_train.py:462-469, training_utils.py:201-216):
  *   g *= clip_coef (clip_coef read from device: min(1, max_norm/(norm+1e-6)));  Adam;  EMA with constant decay. */
 int dp_sumsq_partials(const float* x, long long n, float* partial, int nblocks, void* stream);
