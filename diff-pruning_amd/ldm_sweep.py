@@ -496,14 +496,5 @@ def prune_ldm_model(model, pruning_ratio=0.3, importance=None, global_pruning=Fa
     for m in model.modules():
         if isinstance(m, ldm.CrossAttention):
             channel_groups[m.to_q] = channel_groups[m.to_k] = channel_groups[m.to_v] = m.heads
-    imp = importance if importance is not None else pruning.TaylorImportance()
-    pr = pruning.MagnitudePruner(model, None, importance=imp, global_pruning=global_pruning, iterative_steps=iterative_steps,
-                                 channel_groups=channel_groups, ch_sparsity=pruning_ratio, ignored_layers=[model.out],
-                                 round_to=round_to)
-    for _ in range(iterative_steps):
-        for g in pr.step(interactive=True):
-            g.prune()
-    pruning.fix_static_attributes(model)
-    if getattr(model, '_engine', None) is not None:
-        model._engine.packs.clear()
-    return pr
+    return pruning.prune_every_step(model, importance, iterative_steps, global_pruning=global_pruning, channel_groups=channel_groups,
+                                    ch_sparsity=pruning_ratio, ignored_layers=[model.out], round_to=round_to)

@@ -6,9 +6,18 @@ Mirrors the part of (vendored) torch_pruning the reference's prune scripts use:
   MetaPruner(global_pruning=True) / prune_global                         pruner/algorithms/metapruner.py:126-133,256-297
   Group.prune()                                                          dependency.py:157-185
   function.prune_{conv,linear}_{out,in}_channels, prune_groupnorm_out_channels   pruner/function.py:85-146,168-207,274-302
-Scores are computed on the device by the fused |w*g| channel-reduction kernel (csrc/importance.hip); the
-argsort over the <= 1024 scores of a group and the channel slicing itself are host/plumbing work.  Global pruning scores every
-group in one launch pair and selects on the device (csrc/prune_global.hip).
+
+Slicing: ONE table (`_SLICING`: per layer kind the count attribute, the weight dimension, what else is cut) read by one slicer
+(`_slice_channels`); the `prune_*_channels` names are that slicer bound to a table row, and the batched group slice
+(`_prune_group_batched`, ops.slice_batch) takes its rules from the same rows.
+
+Scoring: ONE core (`_Criterion`).  A criterion is data -- the dp_wg_reduce modes of its conv / linear and GroupNorm members, whether
+the finish takes |.|, whether it averages and normalises -- and the core selects the members that carry a term (`_terms`), describes
+each as the reduction kernels see it (`_desc`) and scores them on the device (csrc/importance.hip) by one of three routes that give
+the same bits: member by member (ops.wg_reduce, then ops.axpby / ops.gather_add), one group in one launch pair (ops.group_score),
+every group in one launch pair (ops.score_groups, csrc/prune_global.hip).  The two batched routes lay their member table out with
+the same function (`_MemberTable.add`); every route ends in the same `_finish`.  The argsort over the <= 1024 scores of a group and
+the bookkeeping of the slicing are host work; global pruning selects on the device (ops.select_smallest).
 
 `TaylorImportance.__call__(group, ch_groups=1)` accepts both this module's groups and groups produced by a real
 `torch_pruning.DependencyGraph` (items `(dep, idxs)` with `dep.target.module` / `dep.handler`), so it can be handed
@@ -50,9 +59,14 @@ def _keep(n, idxs, device):
     return _index_tensor(('keep', n, drop), lambda: [i for i in range(n) if i not in drop], device)
 
 
-def _slice_param(layer, attr, dim, keep):
-    p = getattr(layer, attr)
+def _slice_tensor(layer, attr, dim, keep):
+    """A parameter keeps its accumulated gradient; running statistics are plain buffers.  What the layer does not have (no bias, a
+    non-affine norm, untracked statistics) is None and stays so."""
+    p = getattr(layer, attr, None)
     if p is None:
+        return
+    if not isinstance(p, nn.Parameter):
+        setattr(layer, attr, p.data.index_select(dim, keep))
         return
     g = p.grad.data.index_select(dim, keep) if p.grad is not None else None
     newp = nn.Parameter(p.data.index_select(dim, keep))
@@ -60,127 +74,89 @@ def _slice_param(layer, attr, dim, keep):
     setattr(layer, attr, newp)
 
 
-def prune_conv_out_channels(layer, idxs):
-    keep = _keep(layer.out_channels, idxs, layer.weight.device)
-    layer.out_channels = layer.out_channels - len(set(idxs))
-    _slice_param(layer, 'weight', 0, keep)
-    _slice_param(layer, 'bias', 0, keep)
-    return layer
+# layer kind -> direction -> (attributes that hold the channel count, weight dimension that is cut, what follows on dimension 0).
+# A kind without an 'in' row is cut the same way from either side (function.py gives those one function under two names).
+_ALSO_BIAS, _ALSO_STATS = ('bias',), ('bias', 'running_mean', 'running_var')
+_SLICING = {
+    'conv':           {'out': (('out_channels',), 0, _ALSO_BIAS), 'in': (('in_channels',), 1, ())},
+    'linear':         {'out': (('out_features',), 0, _ALSO_BIAS), 'in': (('in_features',), 1, ())},
+    'conv_transpose': {'out': (('out_channels',), 1, _ALSO_BIAS), 'in': (('in_channels',), 0, ())},        # weight [Cin, Cout, k, k]
+    # one filter per channel: in_channels, out_channels and groups shrink together
+    'depthwise_conv': {'out': (('out_channels', 'in_channels', 'groups'), 0, _ALSO_BIAS)},
+    'groupnorm':      {'out': (('num_channels',), 0, _ALSO_BIAS)},
+    'layernorm':      {'out': (('normalized_shape',), 0, _ALSO_BIAS)},        # the normalised (last) dimension
+    'batchnorm':      {'out': (('num_features',), 0, _ALSO_STATS)},
+    'instancenorm':   {'out': (('num_features',), 0, _ALSO_STATS)},           # statistics, when tracked, so that the module stays usable
+    'prelu':          {'out': (('num_parameters',), 0, ())},
+    'embedding':      {'out': (('embedding_dim',), 1, ())},                   # the columns of the table
+}
+_LAYER_KINDS = ((nn.Linear, 'linear'), (nn.GroupNorm, 'groupnorm'), (nn.LayerNorm, 'layernorm'),
+                (nn.modules.batchnorm._BatchNorm, 'batchnorm'), (nn.modules.instancenorm._InstanceNorm, 'instancenorm'),
+                (nn.PReLU, 'prelu'), (nn.Embedding, 'embedding'))
+_MEMBER_KINDS = {'ln': 'layernorm', 'gn': 'groupnorm', 'bn': 'batchnorm', 'inorm': 'instancenorm', 'prelu': 'prelu',
+                 'embed': 'embedding'}
 
 
-def prune_conv_in_channels(layer, idxs):
-    keep = _keep(layer.in_channels, idxs, layer.weight.device)
-    layer.in_channels = layer.in_channels - len(set(idxs))
-    _slice_param(layer, 'weight', 1, keep)
-    return layer
+def _count(layer, attr):
+    """The channel count behind a count attribute.  Hooks: LayerNorm keeps a shape tuple; a PReLU with one shared slope has none."""
+    n = getattr(layer, attr)
+    if attr == 'normalized_shape':
+        return n[-1]
+    if attr == 'num_parameters' and n == 1:
+        return None
+    return n
 
 
-def prune_linear_out_channels(layer, idxs):
-    keep = _keep(layer.out_features, idxs, layer.weight.device)
-    layer.out_features = layer.out_features - len(set(idxs))
-    _slice_param(layer, 'weight', 0, keep)
-    _slice_param(layer, 'bias', 0, keep)
-    return layer
+def _set_count(layer, attr, n):
+    setattr(layer, attr, tuple(layer.normalized_shape[:-1]) + (n,) if attr == 'normalized_shape' else n)
 
 
-def prune_linear_in_channels(layer, idxs):
-    keep = _keep(layer.in_features, idxs, layer.weight.device)
-    layer.in_features = layer.in_features - len(set(idxs))
-    _slice_param(layer, 'weight', 1, keep)
-    return layer
-
-
-def prune_groupnorm_out_channels(layer, idxs):
-    keep = _keep(layer.num_channels, idxs, layer.weight.device)
-    layer.num_channels = layer.num_channels - len(set(idxs))
-    if layer.affine:
-        _slice_param(layer, 'weight', 0, keep)
-        _slice_param(layer, 'bias', 0, keep)
-    return layer
-
-
-prune_groupnorm_in_channels = prune_groupnorm_out_channels
-
-
-def prune_layernorm_out_channels(layer, idxs):
-    """function.py LayerNormPruner: slice the normalised (last) dimension of weight / bias."""
-    n = layer.normalized_shape[-1]
-    keep = _keep(n, idxs, layer.weight.device)
-    layer.normalized_shape = tuple(layer.normalized_shape[:-1]) + (n - len(set(idxs)),)
-    if layer.elementwise_affine:
-        _slice_param(layer, 'weight', 0, keep)
-        _slice_param(layer, 'bias', 0, keep)
-    return layer
-
-def prune_batchnorm_out_channels(layer, idxs):
-    """function.py BatchnormPruner: slice the running statistics and (if affine) weight / bias."""
-    keep = _keep(layer.num_features, idxs, layer.running_mean.device if layer.running_mean is not None else layer.weight.device)
-    layer.num_features = layer.num_features - len(set(idxs))
-    if layer.track_running_stats:
-        layer.running_mean = layer.running_mean.data.index_select(0, keep)
-        layer.running_var = layer.running_var.data.index_select(0, keep)
-    if layer.affine:
-        _slice_param(layer, 'weight', 0, keep)
-        _slice_param(layer, 'bias', 0, keep)
-    return layer
-
-
-def prune_conv_transpose_out_channels(layer, idxs):
-    """function.py ConvPruner, `transposed` branch: the weight is [Cin, Cout, k, k]."""
-    keep = _keep(layer.out_channels, idxs, layer.weight.device)
-    layer.out_channels = layer.out_channels - len(set(idxs))
-    _slice_param(layer, 'weight', 1, keep)
-    _slice_param(layer, 'bias', 0, keep)
-    return layer
-
-
-def prune_conv_transpose_in_channels(layer, idxs):
-    keep = _keep(layer.in_channels, idxs, layer.weight.device)
-    layer.in_channels = layer.in_channels - len(set(idxs))
-    _slice_param(layer, 'weight', 0, keep)
-    return layer
-
-
-def prune_instancenorm_out_channels(layer, idxs):
-    """function.py InstanceNormPruner (running statistics, when tracked, are sliced too so that the module stays usable)."""
-    dev = layer.weight.device if layer.affine else (layer.running_mean.device if layer.running_mean is not None else 'cpu')
-    keep = _keep(layer.num_features, idxs, dev)
-    layer.num_features = layer.num_features - len(set(idxs))
-    if layer.affine:
-        _slice_param(layer, 'weight', 0, keep)
-        _slice_param(layer, 'bias', 0, keep)
-    if layer.running_mean is not None:
-        layer.running_mean = layer.running_mean.data.index_select(0, keep)
-        layer.running_var = layer.running_var.data.index_select(0, keep)
-    return layer
-
-
-def prune_prelu_out_channels(layer, idxs):
-    """function.py PReLUPruner: a single shared slope is not touched."""
-    if layer.num_parameters == 1:
+def _slice_channels(layer, idxs, rule):
+    """The one slicer: drop the channels `idxs` of `layer` as the table row `rule` says."""
+    attrs, dim, also = rule
+    n = _count(layer, attrs[0])
+    if n is None:
         return layer
-    keep = _keep(layer.num_parameters, idxs, layer.weight.device)
-    layer.num_parameters = layer.num_parameters - len(set(idxs))
-    _slice_param(layer, 'weight', 0, keep)
+    # a non-affine norm has no weight to ask for the device, one without tracked statistics no running_mean; with neither only the count changes
+    held = [t for t in (getattr(layer, 'weight', None), getattr(layer, 'running_mean', None)) if t is not None]
+    keep = _keep(n, idxs, held[0].device if held else 'cpu')
+    for attr in attrs:
+        _set_count(layer, attr, n - len(set(idxs)))
+    _slice_tensor(layer, 'weight', dim, keep)
+    for attr in also:
+        _slice_tensor(layer, attr, 0, keep)
     return layer
 
 
-def prune_embedding_out_channels(layer, idxs):
-    """function.py EmbeddingPruner: the embedding dimension (columns of the table)."""
-    keep = _keep(layer.embedding_dim, idxs, layer.weight.device)
-    layer.embedding_dim = layer.embedding_dim - len(set(idxs))
-    _slice_param(layer, 'weight', 1, keep)
-    return layer
+_FUNCTIONS = {}          # (layer kind, direction) -> its pruning function
 
 
-def prune_depthwise_conv_out_channels(layer, idxs):
-    """function.py DepthwiseConvPruner: one filter per channel, so in_channels, out_channels and groups shrink together."""
-    keep = _keep(layer.out_channels, idxs, layer.weight.device)
-    n = layer.out_channels - len(set(idxs))
-    layer.out_channels = layer.in_channels = layer.groups = n
-    _slice_param(layer, 'weight', 0, keep)
-    _slice_param(layer, 'bias', 0, keep)
-    return layer
+def _pruning_function(kind, direction):
+    """The slicer bound to one table row, under torch_pruning's name for it (`_member_kind` and the tests read handler names)."""
+    def prune(layer, idxs):
+        return _slice_channels(layer, idxs, prune.rule)
+    prune.kind, prune.rule = kind, _SLICING[kind][direction]
+    prune.__name__ = prune.__qualname__ = 'prune_%s_%s_channels' % (kind, direction)
+    prune.__doc__ = 'function.py %s: cut %s, dimension %d of the weight%s.' % (
+        prune.__name__, ' / '.join(prune.rule[0]), prune.rule[1], ''.join(', ' + a for a in prune.rule[2]))
+    _FUNCTIONS[kind, direction] = prune
+    return prune
+
+
+prune_conv_out_channels = _pruning_function('conv', 'out')
+prune_conv_in_channels = _pruning_function('conv', 'in')
+prune_linear_out_channels = _pruning_function('linear', 'out')
+prune_linear_in_channels = _pruning_function('linear', 'in')
+prune_conv_transpose_out_channels = _pruning_function('conv_transpose', 'out')
+prune_conv_transpose_in_channels = _pruning_function('conv_transpose', 'in')
+prune_depthwise_conv_out_channels = _pruning_function('depthwise_conv', 'out')
+prune_groupnorm_out_channels = _pruning_function('groupnorm', 'out')
+prune_groupnorm_in_channels = prune_groupnorm_out_channels
+prune_layernorm_out_channels = _pruning_function('layernorm', 'out')
+prune_batchnorm_out_channels = _pruning_function('batchnorm', 'out')
+prune_instancenorm_out_channels = _pruning_function('instancenorm', 'out')
+prune_prelu_out_channels = _pruning_function('prelu', 'out')
+prune_embedding_out_channels = _pruning_function('embedding', 'out')
 
 
 function = SimpleNamespace(
@@ -196,58 +172,35 @@ function = SimpleNamespace(
     prune_layernorm_out_channels=prune_layernorm_out_channels)
 
 
+for _kind, _rows in _SLICING.items():          # a kind without an 'in' row: the same cut by the same function from either side
+    if 'in' not in _rows:
+        _rows['in'], _FUNCTIONS[_kind, 'in'] = _rows['out'], _FUNCTIONS[_kind, 'out']
+_kind_of_type = {}
+
+
+def _layer_kind(layer):
+    kind = _kind_of_type.get(type(layer))
+    if kind is None:
+        kind = _kind_of_type[type(layer)] = next((k for cls, k in _LAYER_KINDS if isinstance(layer, cls)), 'conv')
+    return kind
+
+
 def _handler_for(layer, kind):
-    if kind == 'ln':
-        return prune_layernorm_out_channels
-    if kind == 'gn':
-        return prune_groupnorm_out_channels
-    if kind == 'bn':
-        return prune_batchnorm_out_channels
-    if kind == 'inorm':
-        return prune_instancenorm_out_channels
-    if kind == 'prelu':
-        return prune_prelu_out_channels
-    if kind == 'embed':
-        return prune_embedding_out_channels
-    if isinstance(layer, nn.modules.conv._ConvNd) and layer.transposed:
-        return prune_conv_transpose_out_channels if kind == 'out' else prune_conv_transpose_in_channels
-    if isinstance(layer, nn.modules.conv._ConvNd) and layer.groups > 1:
-        return prune_depthwise_conv_out_channels
-    if isinstance(layer, nn.Linear):
-        return prune_linear_out_channels if kind == 'out' else prune_linear_in_channels
-    return prune_conv_out_channels if kind == 'out' else prune_conv_in_channels
+    """The pruning function of a member: by the member kind for the pass-through layers, else by what the layer is."""
+    lk = _MEMBER_KINDS.get(kind)
+    if lk is None:
+        lk = _layer_kind(layer)
+        if lk == 'conv' and isinstance(layer, nn.modules.conv._ConvNd) and (layer.transposed or layer.groups > 1):
+            lk = 'conv_transpose' if layer.transposed else 'depthwise_conv'
+    return _FUNCTIONS[lk, 'in' if kind == 'in' else 'out']
 
 
 def _out_channels(layer):
-    if isinstance(layer, nn.Linear):
-        return layer.out_features
-    if isinstance(layer, nn.GroupNorm):
-        return layer.num_channels
-    if isinstance(layer, nn.LayerNorm):
-        return layer.normalized_shape[-1]
-    if isinstance(layer, (nn.modules.batchnorm._BatchNorm, nn.modules.instancenorm._InstanceNorm)):
-        return layer.num_features
-    if isinstance(layer, nn.PReLU):
-        return layer.num_parameters if layer.num_parameters > 1 else None
-    if isinstance(layer, nn.Embedding):
-        return layer.embedding_dim
-    return layer.out_channels
+    return _count(layer, _SLICING[_layer_kind(layer)]['out'][0][0])
 
 
 def _in_channels(layer):
-    if isinstance(layer, nn.Linear):
-        return layer.in_features
-    if isinstance(layer, nn.GroupNorm):
-        return layer.num_channels
-    if isinstance(layer, nn.LayerNorm):
-        return layer.normalized_shape[-1]
-    if isinstance(layer, (nn.modules.batchnorm._BatchNorm, nn.modules.instancenorm._InstanceNorm)):
-        return layer.num_features
-    if isinstance(layer, nn.PReLU):
-        return layer.num_parameters if layer.num_parameters > 1 else None
-    if isinstance(layer, nn.Embedding):
-        return layer.embedding_dim
-    return layer.in_channels
+    return _count(layer, _SLICING[_layer_kind(layer)]['in'][0][0])
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -301,39 +254,26 @@ class Group:
 
     def details(self):
         return ['%s:%s(%d)' % (dep.kind, dep.target.name, len(idxs)) for dep, idxs in self._items]
-
-
 PRUNE_BATCH = not os.environ.get('DP_NO_PRUNE_BATCH')
-_BATCH_RULES = {}        # handler -> (weight dim, slices the bias too, attribute that holds the channel count)
-
-
-def _batch_rules():
-    if not _BATCH_RULES:
-        _BATCH_RULES.update({
-            prune_conv_out_channels: (0, True, 'out_channels'), prune_conv_in_channels: (1, False, 'in_channels'),
-            prune_linear_out_channels: (0, True, 'out_features'), prune_linear_in_channels: (1, False, 'in_features'),
-            prune_groupnorm_out_channels: (0, True, 'num_channels')})
-    return _BATCH_RULES
+_BATCHED_KINDS = ('conv', 'linear', 'groupnorm')
 
 
 def _prune_group_batched(items):
     """function.py:85-146,168-207,274-302 for ALL members of a group in one kernel launch (ops.slice_batch): every weight, bias
     and accumulated gradient keeps its un-pruned channels; the layers' channel attributes are updated as the per-member
-    functions do.  Returns False (nothing touched) when a member is not a plain Conv2d / Linear / GroupNorm on the device, or
-    when one tensor would be sliced twice in the group -- the caller then prunes member by member."""
+    functions do.  Returns False (nothing touched) when a member is not a plain Conv2d / Linear / affine GroupNorm on the device
+    (`_BATCHED_KINDS` rows of `_SLICING`), or when one tensor would be sliced twice in the group -- the caller then prunes member
+    by member."""
     if not PRUNE_BATCH or not hasattr(ops, 'slice_batch') or not items:
         return False
-    rules = _batch_rules()
     plan, seen = [], set()
     for dep, idxs in items:
-        rule = rules.get(dep.handler)
         layer = dep.target.module
-        if rule is None or getattr(layer, 'transposed', False) or getattr(layer, 'groups', 1) != 1:
+        if getattr(dep.handler, 'kind', None) not in _BATCHED_KINDS or getattr(layer, 'transposed', False) \
+                or getattr(layer, 'groups', 1) != 1 or layer.weight is None:
             return False
-        dim, with_bias, attr = rule
-        if isinstance(layer, nn.GroupNorm) and not layer.affine:
-            return False
-        names = ['weight'] + (['bias'] if with_bias and getattr(layer, 'bias', None) is not None else [])
+        (attr,), dim, also = dep.handler.rule
+        names = ['weight'] + [nm for nm in also if getattr(layer, nm, None) is not None]
         for nm in names:
             if (id(layer), nm) in seen or (getattr(layer, nm).device.type != 'cuda' and not getattr(ops, 'IS_MOCK', False)):
                 return False          # host-side structure edits (history replay on a CPU model) slice member by member
@@ -406,8 +346,8 @@ def _member_kind(dep):
 # importance criteria
 # --------------------------------------------------------------------------------------------------------
 class Importance(abc.ABC):
-    @abc.abstractclassmethod
-    def __call__(self, group):
+    @abc.abstractmethod
+    def __call__(self, group, ch_groups=1):
         raise NotImplementedError
 
     def score_all(self, groups, ch_groups=None):
@@ -417,71 +357,199 @@ class Importance(abc.ABC):
         return [self(g, ch_groups=c) for g, c in zip(groups, chg)]
 
 
-def _score_all_batched(crit, groups):
-    """Every group's member reductions and member sums in ONE launch pair (ops.score_groups, csrc/prune_global.hip): the member
-    descriptors of `_score_batched`, with offsets into one scratch / index / score vector shared by all groups -- the same
-    per-member reductions in the same member order as the criterion's `__call__`, hence the same bits -- then the criterion's own
-    per-group finish (`_finish`: group_reduction / normalizer / |.|).  `crit` supplies `_terms(group)` -> [(layer, kind, idxs)],
-    `_desc(layer, kind)` -> (w, g, R, C, T, dim, mode).  Returns the list of per-group scores, or None (not applicable: the
-    caller scores group by group)."""
-    if not PRUNE_BATCH or not hasattr(ops, 'score_groups') or not getattr(crit, '_batchable', True):
-        return None
-    per_group, idx_host, need, dev = [], [], 0, None
-    for group in groups:
-        terms = crit._terms(group)
-        if not terms:
-            per_group.append(None)
-            continue
-        n0 = len(terms[0][2])
-        members = []
-        for layer, kind, idxs in terms:
-            if len(idxs) != n0:             # importance.py:422-426: mis-sized members are dropped
-                continue
-            w, g, R, Cc, T, dim, mode = crit._desc(layer, kind)
-            dev = w.device if dev is None else dev
-            if not (w.is_contiguous() and g.is_contiguous()) or w.device != dev or g.device != dev:
-                return None
-            cols = mode != 3 and dim == 1
-            n_full = Cc if cols else R
-            m = dict(w=w, g=g, R=R, C=Cc, T=T, dim=dim, mode=mode, full_off=0, col_off=0, idx_off=-1)
-            if cols:
-                m['col_off'] = need
-                need += Cc * T
-            else:
-                m['full_off'] = need
-                need += n_full
-            if not (n_full == n0 and idxs[0] == 0 and idxs[-1] == n0 - 1):
-                if idxs[0] < 0 or idxs[-1] >= n_full:
-                    raise IndexError('group member index outside its layer (%d channels)' % n_full)
-                m['idx_off'] = len(idx_host)
-                idx_host.extend(idxs)
-            members.append(m)
-        per_group.append((members, n0))
-    live = [pg for pg in per_group if pg is not None]
-    if not live:
-        return [None] * len(groups)
-    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
-    idx_dev = torch.from_numpy(np.asarray(idx_host, dtype=np.int64)).to(dev) if idx_host else None
-    scores = torch.empty(sum(n0 for _, n0 in live), dtype=torch.float32, device=dev)
-    ops.score_groups(live, idx_dev, scratch, scores)
-    out, off = [], 0
-    for pg in per_group:
-        if pg is None:
-            out.append(None)
-            continue
-        members, n0 = pg
-        out.append(crit._finish(scores[off:off + n0], len(members)))
-        off += n0
-    return out
-
-
 _MODES = {'sum_sq': 0, 'sum_abs': 1, 'abs_sum': 2}
 _NO_TERM = ('ln', 'bn', 'inorm', 'prelu', 'embed')                     # member kinds the vendored criteria have no branch for
 _OUT_KINDS = ('out', 'gn', 'ln', 'bn', 'inorm', 'prelu', 'embed')      # members pruned through an out-channel pruning function
 _F_SQ, _F_ABS, _F_SIGNED, _F_GN_ABS, _F_GRAD_SQ, _F_SUM = 0, 1, 2, 3, 4, 5      # dp_wg_reduce modes (include/dp_hip.h)
 
 
-class TaylorImportance(Importance):
+class _MemberTable:
+    """The member table of ops.group_score (one group) / ops.score_groups (every group): each member's reduction lands in a
+    scratch vector shared by the table, an index-mapped member reads its channels through a shared index list."""
+
+    def __init__(self):
+        self.need, self.idx, self.dev = 0, [], None           # scratch floats, index entries, the device of the first member
+
+    def add(self, members, n0):
+        """Lay out one group of n0 channels.  members: (w, g, R, C, T, dim, (mode,), idxs) each -- a [R, C, T] view of w and g reduced
+        in dp_wg_reduce `mode` to R values (dim 0, and mode 3) or C values (dim 1, through C * T column sums), of which `idxs`
+        (ascending) are this group's; all of them in order when idxs is 0 .. n0 - 1 of an n0-channel layer.  Returns the kernels'
+        member dicts, or None for a tensor the kernels cannot take (not contiguous, another device); an index outside the layer
+        is refused."""
+        out = []
+        for w, g, R, Cc, T, dim, (mode,), idxs in members:
+            self.dev = w.device if self.dev is None else self.dev
+            if not (w.is_contiguous() and g.is_contiguous()) or w.device != self.dev or g.device != self.dev:
+                return None
+            cols = mode != _F_GN_ABS and dim == 1
+            n_full = Cc if cols else R
+            m = dict(w=w, g=g, R=R, C=Cc, T=T, dim=dim, mode=mode, full_off=0, col_off=0, idx_off=-1)
+            m['col_off' if cols else 'full_off'] = self.need
+            self.need += Cc * T if cols else n_full
+            if not (n_full == n0 and idxs[0] == 0 and idxs[-1] == n0 - 1):
+                if idxs[0] < 0 or idxs[-1] >= n_full:
+                    raise IndexError('group member index outside its layer (%d channels)' % n_full)
+                m['idx_off'] = len(self.idx)
+                self.idx.extend(idxs)
+            out.append(m)
+        return out
+
+    def index_tensor(self):
+        return torch.from_numpy(np.asarray(self.idx, dtype=np.int64)).to(self.dev) if self.idx else None
+
+
+class _Criterion(Importance):
+    """The scoring core.  Every member that carries a term contributes the sum over its other dims of f(w, g) -- one dp_wg_reduce
+    pass per mode of `conv_modes` (conv / linear members) or `gn_modes` (GroupNorm members; empty: they carry no term) -- members
+    whose length differs from the root's are dropped (importance.py:422-426), the rest are summed at their channel positions, and
+    `_finish` ends it: |.| when `final_abs`; the mean over the members and the division by the mean when `mean_finish`.
+    `group_batched`: `__call__` scores a group through ops.group_score (else member by member)."""
+    conv_modes = (_F_SQ,)
+    gn_modes = (_F_ABS,)
+    final_abs = False
+    mean_finish = False
+    group_batched = False
+
+    def __init__(self, group_reduction='mean', normalizer='mean'):      # read only where mean_finish, as in the reference
+        self.group_reduction, self.normalizer = group_reduction, normalizer
+        self._scratch = None
+
+    def _grown_scratch(self, need, dev):
+        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
+            self._scratch = torch.empty(max(need, 1 << 16), dtype=torch.float32, device=dev)
+        return self._scratch
+
+    def _grad(self, layer):
+        g = layer.weight.grad
+        if g is None:
+            raise RuntimeError('%s needs accumulated gradients (run the sweep before pruner.step())' % type(self).__name__)
+        return g.data
+
+    def _terms(self, group):
+        """The members that carry a term: [(layer, kind, idxs)] in group order (each index list sorted in place)."""
+        terms = []
+        for dep, idxs in group:
+            idxs.sort()
+            kind = _member_kind(dep)
+            if kind is None or kind in _NO_TERM:      # LayerNorm / BatchNorm / ... members carry no term (importance.py:383-418)
+                continue
+            layer = dep.target.module
+            if kind == 'gn' and (not layer.affine or not self.gn_modes):
+                continue
+            terms.append((layer, kind, idxs))
+        return terms
+
+    def _desc(self, layer, kind):
+        """-> (w, g, R, C, T, dim, modes): the member as dp_wg_reduce sees it."""
+        w, g = layer.weight.data, self._grad(layer)
+        if kind == 'gn':
+            return w, g, w.shape[0], 1, 1, 0, self.gn_modes
+        dim = 0 if kind == 'out' else 1
+        if getattr(layer, 'transposed', False):        # ConvTranspose: weight [Cin, Cout, k, k] (importance.py:390-392,404-406)
+            dim = 1 - dim
+        T = 1
+        for v in w.shape[2:]:
+            T *= v
+        return w, g, w.shape[0], w.shape[1] if w.dim() > 1 else 1, T, dim, self.conv_modes
+
+    def _members(self, terms, n0):
+        for layer, kind, idxs in terms:
+            if len(idxs) == n0:
+                yield self._desc(layer, kind) + (idxs,)
+
+    @property
+    def _batchable(self):
+        """One reduction per member: a member that accumulates two modes (FullTaylorImportance(order=2)) adds them BEFORE the
+        member sum, which the one-pass member table cannot express bit for bit -> scored member by member."""
+        return len(self.conv_modes) == 1 and len(self.gn_modes) <= 1
+
+    def _score_members(self, terms, n0, dev):
+        """Member by member: ops.wg_reduce per mode, then ops.axpby (all channels in order) or ops.gather_add."""
+        score, used = torch.zeros(n0, dtype=torch.float32, device=dev), 0
+        for w, g, R, Cc, T, dim, modes, idxs in self._members(terms, n0):
+            n_full = Cc if dim == 1 else R
+            full = torch.empty(n_full, dtype=torch.float32, device=w.device)
+            scratch = self._grown_scratch(Cc * T, w.device) if dim == 1 else None
+            w, g = w.contiguous(), g.contiguous()
+            if modes != (_F_GN_ABS,):                   # mode 3 takes the 1-D GroupNorm weight as it is
+                w, g = w.view(R, Cc, T), g.view(R, Cc, T)
+            for i, mode in enumerate(modes):
+                ops.wg_reduce(w, g, dim, mode, full, i > 0, scratch)
+            if n_full == n0 and idxs[0] == 0 and idxs[-1] == n0 - 1:
+                ops.axpby(full, 1.0, score, 1.0)
+            else:
+                ops.gather_add(full, _index_tensor(('idx', tuple(idxs)), lambda: idxs, dev), score)
+            used += 1
+        return score, used
+
+    def _score_group(self, terms, n0):
+        """All members of the group through ops.group_score (two launches): the same per-member reductions in the same member
+        order as `_score_members`, hence the same bits.  Returns (score, members used) or None (not applicable)."""
+        table = _MemberTable()
+        members = table.add(self._members(terms, n0), n0)
+        if not members:
+            return None
+        score = torch.empty(n0, dtype=torch.float32, device=table.dev)
+        ops.group_score(members, n0, table.index_tensor(), self._grown_scratch(table.need, table.dev), score)
+        return score, len(members)
+
+    def _finish(self, score, used):
+        if self.final_abs:           # |score|: signed row "sum" over one column with the abs-after-sum mode
+            out = torch.empty_like(score)
+            ops.wg_reduce(score.view(-1, 1), torch.ones_like(score).view(-1, 1), 0, _F_SIGNED, out, False)
+            score = out
+        if self.mean_finish:
+            if self.group_reduction == 'mean':
+                ops.axpby(score, 0.0, score, 1.0 / used)
+            if self.normalizer == 'mean':
+                mean = float(score.mean())
+                ops.axpby(score, 0.0, score, 1.0 / mean)
+        return score
+
+    @torch.no_grad()
+    def __call__(self, group, ch_groups=1):
+        terms = self._terms(group)
+        if not terms:
+            return None
+        n0 = len(terms[0][2])
+        batched = self.group_batched and self._batchable and PRUNE_BATCH and hasattr(ops, 'group_score')
+        got = self._score_group(terms, n0) if batched else None            # None: member by member
+        return self._finish(*(got or self._score_members(terms, n0, terms[0][0].weight.device)))
+
+    @torch.no_grad()
+    def score_all(self, groups, ch_groups=None):
+        """Every group's member reductions and member sums in ONE launch pair (ops.score_groups, csrc/prune_global.hip): the member
+        table of `_score_group` with ONE scratch / index / score vector shared by all groups -- the same per-member reductions in
+        the same member order as `__call__`, hence the same bits -- then the same per-group finish.  Where that is not applicable
+        (no batched kernels, two reductions per member, a tensor the kernels cannot take) the criterion is called group by group."""
+        if not PRUNE_BATCH or not hasattr(ops, 'score_groups') or not self._batchable:
+            return super().score_all(groups, ch_groups)
+        table, per_group = _MemberTable(), []
+        for group in groups:
+            terms = self._terms(group)
+            n0 = len(terms[0][2]) if terms else 0
+            members = table.add(self._members(terms, n0), n0)
+            if members is None:
+                return super().score_all(groups, ch_groups)
+            per_group.append((members, n0) if terms else None)
+        live = [pg for pg in per_group if pg is not None]
+        if not live:
+            return [None] * len(groups)
+        scores = torch.empty(sum(n0 for _, n0 in live), dtype=torch.float32, device=table.dev)
+        ops.score_groups(live, table.index_tensor(), self._grown_scratch(table.need, table.dev), scores)
+        out, off = [], 0
+        for pg in per_group:
+            if pg is None:
+                out.append(None)
+                continue
+            members, n0 = pg
+            part = scores[off:off + n0]
+            out.append(self._finish(part.clone() if self.mean_finish else part, len(members)))      # normalised in place: a tensor of its own
+            off += n0
+        return out
+
+
+class TaylorImportance(_Criterion):
     """First-order Taylor importance on the device.
 
     multivariable=None  -> the reference's vendored criterion (importance.py:375-434): conv/linear members
@@ -495,278 +563,19 @@ class TaylorImportance(Importance):
                            era only had a BatchNorm branch (prune_batchnorm_out_channels), GroupNorm members matched no
                            branch and added nothing -> default False for the multivariable modes (recalled, unpinned).
     `sweep.prune_model` defaults to the vendored ('sum_sq') criterion: the only one pinned by reference outputs."""
+    group_batched = True
 
     def __init__(self, group_reduction='mean', normalizer='mean', multivariable=None, groupnorm_term=None):
-        self.group_reduction, self.normalizer, self.multivariable = group_reduction, normalizer, multivariable
+        super().__init__(group_reduction, normalizer)
+        self.multivariable = multivariable
         self.mode = 'sum_sq' if multivariable is None else ('abs_sum' if multivariable else 'sum_abs')
         self.groupnorm_term = (multivariable is None) if groupnorm_term is None else bool(groupnorm_term)
-        self._scratch = None
-
-    def _member_score(self, layer, kind, idxs, out_len):
-        w = layer.weight.data
-        g = layer.weight.grad
-        if g is None:
-            raise RuntimeError('TaylorImportance needs accumulated gradients (run the sweep before pruner.step())')
-        g = g.data
-        dev = w.device
-        if kind == 'gn':
-            full = torch.empty(w.shape[0], dtype=torch.float32, device=dev)
-            ops.wg_reduce(w, g, 0, 3, full, False)
-            n_full = w.shape[0]
-        else:
-            dim = 0 if kind == 'out' else 1
-            if getattr(layer, 'transposed', False):        # ConvTranspose: weight [Cin, Cout, k, k] (importance.py:390-392,404-406)
-                dim = 1 - dim
-            n_full = w.shape[dim]
-            full = torch.empty(n_full, dtype=torch.float32, device=dev)
-            if dim == 1:
-                need = w.numel() // w.shape[0]
-                if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
-                    self._scratch = torch.empty(max(need, 1 << 16), dtype=torch.float32, device=dev)
-            ops.wg_reduce(w.contiguous(), g.contiguous(), dim, _MODES[self.mode], full, False, self._scratch)
-        return full, n_full
-
-    def _score_batched(self, terms, n0, dev):
-        """All members of the group through ops.group_score (two launches): the same per-member reductions and the same
-        member order as the loop below, hence the same bits.  Returns (score, members used) or None (not applicable)."""
-        members, idx_host, need = [], [], 0
-        for layer, kind, idxs in terms:
-            if len(idxs) != n0:             # importance.py:422-426: mis-sized members are dropped
-                continue
-            w, g = layer.weight.data, layer.weight.grad
-            if g is None:
-                raise RuntimeError('TaylorImportance needs accumulated gradients (run the sweep before pruner.step())')
-            g = g.data
-            if not (w.is_contiguous() and g.is_contiguous()) or w.device != dev:
-                return None
-            if kind == 'gn':
-                m = dict(R=w.shape[0], C=1, T=1, dim=0, mode=3)
-                n_full = w.shape[0]
-            else:
-                dim = 0 if kind == 'out' else 1
-                if getattr(layer, 'transposed', False):
-                    dim = 1 - dim
-                T = 1
-                for v in w.shape[2:]:
-                    T *= v
-                m = dict(R=w.shape[0], C=w.shape[1] if w.dim() > 1 else 1, T=T, dim=dim, mode=_MODES[self.mode])
-                n_full = w.shape[dim]
-            m.update(w=w, g=g, full_off=0, col_off=0, idx_off=-1)
-            if m['mode'] != 3 and m['dim'] == 1:
-                m['col_off'] = need
-                need += m['C'] * m['T']
-            else:
-                m['full_off'] = need
-                need += n_full
-            if not (n_full == n0 and idxs[0] == 0 and idxs[-1] == n0 - 1):
-                m['idx_off'] = len(idx_host)
-                idx_host.extend(idxs)
-            members.append(m)
-        if not members:
-            return None
-        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
-            self._scratch = torch.empty(max(need, 1 << 16), dtype=torch.float32, device=dev)
-        idx_dev = torch.from_numpy(np.asarray(idx_host, dtype=np.int64)).to(dev) if idx_host else None
-        score = torch.empty(n0, dtype=torch.float32, device=dev)
-        ops.group_score(members, n0, idx_dev, self._scratch, score)
-        return score, len(members)
-
-    def _terms(self, group):
-        """The members that carry a term, as `__call__` selects them."""
-        terms = []
-        for dep, idxs in group:
-            idxs.sort()
-            kind = _member_kind(dep)
-            if kind is None or kind in _NO_TERM:
-                continue
-            layer = dep.target.module
-            if kind == 'gn' and (not layer.affine or not self.groupnorm_term):
-                continue
-            terms.append((layer, kind, idxs))
-        return terms
-
-    def _desc(self, layer, kind):
-        w, g = layer.weight.data, layer.weight.grad
-        if g is None:
-            raise RuntimeError('TaylorImportance needs accumulated gradients (run the sweep before pruner.step())')
-        g = g.data
-        if kind == 'gn':
-            return w, g, w.shape[0], 1, 1, 0, 3
-        dim = 0 if kind == 'out' else 1
-        if getattr(layer, 'transposed', False):
-            dim = 1 - dim
-        T = 1
-        for v in w.shape[2:]:
-            T *= v
-        return w, g, w.shape[0], w.shape[1] if w.dim() > 1 else 1, T, dim, _MODES[self.mode]
-
-    def _finish(self, score, used):
-        if self.multivariable is not None:
-            score = score.clone()               # a tensor of its own, as `__call__` normalises one
-            if self.group_reduction == 'mean':
-                ops.axpby(score, 0.0, score, 1.0 / used)
-            if self.normalizer == 'mean':
-                mean = float(score.mean())
-                ops.axpby(score, 0.0, score, 1.0 / mean)
-        return score
-
-    @torch.no_grad()
-    def score_all(self, groups, ch_groups=None):
-        got = _score_all_batched(self, groups)
-        return got if got is not None else super().score_all(groups, ch_groups)
-
-    @torch.no_grad()
-    def __call__(self, group, ch_groups=1):
-        terms = []
-        for dep, idxs in group:
-            idxs.sort()
-            kind = _member_kind(dep)
-            if kind is None or kind in _NO_TERM:      # LayerNorm / BatchNorm / ... members carry no term (importance.py:383-418)
-                continue
-            layer = dep.target.module
-            if kind == 'gn' and (not layer.affine or not self.groupnorm_term):
-                continue
-            terms.append((layer, kind, idxs))
-        if not terms:
-            return None
-        n0 = len(terms[0][2])
-        dev = terms[0][0].weight.device
-        batched = self._score_batched(terms, n0, dev) if PRUNE_BATCH and hasattr(ops, 'group_score') else None      # None: member by member
-        score = torch.zeros(n0, dtype=torch.float32, device=dev) if batched is None else batched[0]
-        used = 0 if batched is None else batched[1]
-        for layer, kind, idxs in (terms if batched is None else ()):
-            if len(idxs) != n0:             # importance.py:422-426: mis-sized members are dropped
-                continue
-            full, n_full = self._member_score(layer, kind, idxs, n0)
-            if n_full == n0 and idxs[0] == 0 and idxs[-1] == n0 - 1:
-                ops.axpby(full, 1.0, score, 1.0)
-            else:
-                ops.gather_add(full, _index_tensor(('idx', tuple(idxs)), lambda: idxs, dev), score)
-            used += 1
-        if self.multivariable is not None:
-            if self.group_reduction == 'mean':
-                ops.axpby(score, 0.0, score, 1.0 / used)
-            if self.normalizer == 'mean':
-                mean = float(score.mean())
-                ops.axpby(score, 0.0, score, 1.0 / mean)
-        return score
+        self.conv_modes = (_MODES[self.mode],)
+        self.gn_modes = (_F_GN_ABS,) if self.groupnorm_term else ()
+        self.mean_finish = multivariable is not None
 
 
-class _GradCriterion(Importance):
-    """Shared driver of the gradient criteria selectable in ddpm_exp/prune.py:193-208: every member contributes
-    sum over its other dims of f(w, g) (one or two dp_wg_reduce passes), length-mismatched members are dropped, members
-    are summed, optionally |.| at the end.  conv_modes / gn_modes: dp_wg_reduce modes accumulated per member."""
-    conv_modes = (_F_SQ,)
-    gn_modes = (_F_ABS,)
-    final_abs = False
-
-    def __init__(self, group_reduction='mean', normalizer='mean'):      # accepted and unused, as in the reference
-        self.group_reduction, self.normalizer = group_reduction, normalizer
-        self._scratch = None
-
-    def _member_score(self, layer, kind):
-        w, g = layer.weight.data, layer.weight.grad
-        if g is None:
-            raise RuntimeError('%s needs accumulated gradients (run the sweep before pruner.step())' % type(self).__name__)
-        g = g.data
-        if kind == 'gn':
-            w, g, dim, modes = w.reshape(-1, 1), g.reshape(-1, 1), 0, self.gn_modes
-        else:
-            dim, modes = (0 if kind == 'out' else 1), self.conv_modes
-            if getattr(layer, 'transposed', False):
-                dim = 1 - dim
-        n_full = w.shape[dim]
-        full = torch.empty(n_full, dtype=torch.float32, device=w.device)
-        if dim == 1:
-            need = w.numel() // w.shape[0]
-            if self._scratch is None or self._scratch.numel() < need or self._scratch.device != w.device:
-                self._scratch = torch.empty(max(need, 1 << 16), dtype=torch.float32, device=w.device)
-        for i, m in enumerate(modes):
-            ops.wg_reduce(w.contiguous(), g.contiguous(), dim, m, full, i > 0, self._scratch)
-        return full, n_full
-
-    @property
-    def _batchable(self):
-        """One reduction per member: a member that accumulates two modes (FullTaylorImportance(order=2)) adds them BEFORE the
-        member sum, which the one-pass table cannot express bit for bit -> scored group by group."""
-        return len(self.conv_modes) == 1 and len(self.gn_modes) <= 1
-
-    def _terms(self, group):
-        terms = []
-        for dep, idxs in group:
-            idxs.sort()
-            kind = _member_kind(dep)
-            if kind is None or kind in _NO_TERM:
-                continue
-            layer = dep.target.module
-            if kind == 'gn' and (not layer.affine or not self.gn_modes):
-                continue
-            terms.append((layer, kind, idxs))
-        return terms
-
-    def _desc(self, layer, kind):
-        w, g = layer.weight.data, layer.weight.grad
-        if g is None:
-            raise RuntimeError('%s needs accumulated gradients (run the sweep before pruner.step())' % type(self).__name__)
-        g = g.data
-        if kind == 'gn':                        # `_member_score`: the [n, 1] view through the row reduction
-            return w, g, w.shape[0], 1, 1, 0, self.gn_modes[0]
-        dim = 0 if kind == 'out' else 1
-        if getattr(layer, 'transposed', False):
-            dim = 1 - dim
-        T = 1
-        for v in w.shape[2:]:
-            T *= v
-        return w, g, w.shape[0], w.shape[1] if w.dim() > 1 else 1, T, dim, self.conv_modes[0]
-
-    def _finish(self, score, used):
-        self._used = used
-        if self.final_abs:
-            out = torch.empty_like(score)
-            ops.wg_reduce(score.view(-1, 1), torch.ones_like(score).view(-1, 1), 0, _F_SIGNED, out, False)
-            score = out
-        return score
-
-    @torch.no_grad()
-    def score_all(self, groups, ch_groups=None):
-        got = _score_all_batched(self, groups)
-        return got if got is not None else super().score_all(groups, ch_groups)
-
-    @torch.no_grad()
-    def __call__(self, group, ch_groups=1):
-        terms = []
-        for dep, idxs in group:
-            idxs.sort()
-            kind = _member_kind(dep)
-            if kind is None or kind in _NO_TERM:
-                continue
-            layer = dep.target.module
-            if kind == 'gn' and (not layer.affine or not self.gn_modes):
-                continue
-            terms.append((layer, kind, idxs))
-        if not terms:
-            return None
-        n0 = len(terms[0][2])
-        dev = terms[0][0].weight.device
-        score = torch.zeros(n0, dtype=torch.float32, device=dev)
-        self._used = 0
-        for layer, kind, idxs in terms:
-            if len(idxs) != n0:
-                continue
-            full, n_full = self._member_score(layer, kind)
-            if n_full == n0 and idxs[0] == 0 and idxs[-1] == n0 - 1:
-                ops.axpby(full, 1.0, score, 1.0)
-            else:
-                ops.gather_add(full, _index_tensor(('idx', tuple(idxs)), lambda: idxs, dev), score)
-            self._used += 1
-        if self.final_abs:           # |score|: signed row "sum" over one column with the abs-after-sum mode
-            out = torch.empty_like(score)
-            ops.wg_reduce(score.view(-1, 1), torch.ones_like(score).view(-1, 1), 0, _F_SIGNED, out, False)
-            score = out
-        return score
-
-
-class FullTaylorImportance(_GradCriterion):
+class FullTaylorImportance(_Criterion):
     """importance.py:482-548: order 1: sum w*g; order 2: sum w*g + sum (w*g)^2; |.| after the members are summed."""
     final_abs = True
 
@@ -779,7 +588,7 @@ class FullTaylorImportance(_GradCriterion):
         self.gn_modes = self.conv_modes
 
 
-class AbsTaylorImportance(_GradCriterion):
+class AbsTaylorImportance(_Criterion):
     """importance.py:611-670: sum |w*g| per member, plain sum over members."""
     conv_modes = (_F_ABS,)
     gn_modes = (_F_ABS,)
@@ -788,17 +597,18 @@ class AbsTaylorImportance(_GradCriterion):
         super().__init__(group_reduction, normalizer)
 
 
-class FisherImportance(_GradCriterion):
+class FisherImportance(_Criterion):
     """importance.py:715-781: conv / linear members sum g^2, GroupNorm members (w*g)^2."""
     conv_modes = (_F_GRAD_SQ,)
     gn_modes = (_F_SQ,)
 
 
-class MagnitudeImportance(_GradCriterion):
+class MagnitudeImportance(_Criterion):
     """importance.py:59-126: sum |w|^p per conv / linear member (GroupNorm members carry no term: the vendored class only
-    matches BatchNorm), mean over members, divided by its mean.  p = 2 runs on the fused reduction with g := w."""
+    matches BatchNorm), mean over members, divided by its mean.  p = 2 runs on the fused reduction with g := w: |w*w| = |w|^2."""
     conv_modes = (_F_ABS,)
     gn_modes = ()
+    mean_finish = True
 
     def __init__(self, p=2, group_reduction='mean', normalizer='mean'):
         super().__init__(group_reduction, normalizer)
@@ -806,43 +616,8 @@ class MagnitudeImportance(_GradCriterion):
             raise NotImplementedError('MagnitudeImportance: only p = 2 (the reference default) is built')
         self.p = p
 
-    def _member_score(self, layer, kind):
-        w = layer.weight.data.contiguous()
-        dim = 0 if kind == 'out' else 1
-        n_full = w.shape[dim]
-        full = torch.empty(n_full, dtype=torch.float32, device=w.device)
-        if dim == 1:
-            need = w.numel() // w.shape[0]
-            if self._scratch is None or self._scratch.numel() < need or self._scratch.device != w.device:
-                self._scratch = torch.empty(max(need, 1 << 16), dtype=torch.float32, device=w.device)
-        ops.wg_reduce(w, w, dim, _F_ABS, full, False, self._scratch)          # |w*w| = |w|^2
-        return full, n_full
-
-    def _desc(self, layer, kind):
-        w = layer.weight.data
-        T = 1
-        for v in w.shape[2:]:
-            T *= v
-        return w, w, w.shape[0], w.shape[1] if w.dim() > 1 else 1, T, 0 if kind == 'out' else 1, _F_ABS
-
-    def _finish(self, score, used):
-        score = super()._finish(score, used).clone()
-        if self.group_reduction == 'mean':
-            ops.axpby(score, 0.0, score, 1.0 / used)
-        if self.normalizer == 'mean':
-            ops.axpby(score, 0.0, score, 1.0 / float(score.mean()))
-        return score
-
-    @torch.no_grad()
-    def __call__(self, group, ch_groups=1):
-        score = super().__call__(group, ch_groups)
-        if score is None:
-            return None
-        if self.group_reduction == 'mean':
-            ops.axpby(score, 0.0, score, 1.0 / self._used)
-        if self.normalizer == 'mean':
-            ops.axpby(score, 0.0, score, 1.0 / float(score.mean()))
-        return score
+    def _grad(self, layer):
+        return layer.weight.data
 
 
 class RandomImportance(Importance):
@@ -1130,6 +905,21 @@ def fix_static_attributes(model):
     for m in model.modules():
         if hasattr(m, 'channels') and hasattr(m, 'conv') and isinstance(m.conv, nn.Conv2d):
             m.channels = m.conv.in_channels
+
+
+def prune_every_step(model, importance=None, iterative_steps=1, **pruner_args):
+    """What the prune scripts do after the importance pass (ddpm_prune.py:79-116, prune_ldm.py:70-100): build the pruner (the
+    vendored Taylor criterion unless one is given), prune every group each `step()` yields, then fix the static `channels`
+    attributes and drop the engine's weight packs, which describe the old shapes.  Returns the pruner."""
+    pr = MagnitudePruner(model, None, importance=importance if importance is not None else TaylorImportance(),
+                         iterative_steps=iterative_steps, **pruner_args)
+    for _ in range(iterative_steps):
+        for g in pr.step(interactive=True):
+            g.prune()
+    fix_static_attributes(model)
+    if getattr(model, '_engine', None) is not None:
+        model._engine.packs.clear()
+    return pr
 
 
 def count_ops_and_params(model, example_inputs=None):

@@ -527,14 +527,6 @@ def prune_model(model, pruning_ratio=0.3, importance=None, ignored_layers=None, 
     global_pruning: one ranking across every group (metapruner.py:256-297) instead of `pruning_ratio` per layer;
     iterative_steps: that many `step()`s over the gradients already accumulated (linear sparsity schedule)."""
     from . import pruning
-    imp = importance if importance is not None else pruning.TaylorImportance()
-    pr = pruning.MagnitudePruner(model, None, importance=imp, global_pruning=global_pruning, iterative_steps=iterative_steps,
-                                 channel_groups=channel_groups or {}, ch_sparsity=pruning_ratio,
-                                 ignored_layers=ignored_layers if ignored_layers is not None else [model.conv_out])
-    for _ in range(iterative_steps):
-        for g in pr.step(interactive=True):
-            g.prune()
-    pruning.fix_static_attributes(model)
-    if getattr(model, '_engine', None) is not None:
-        model._engine.packs.clear()
-    return pr
+    return pruning.prune_every_step(model, importance, iterative_steps, global_pruning=global_pruning,
+                                    channel_groups=channel_groups or {}, ch_sparsity=pruning_ratio,
+                                    ignored_layers=ignored_layers if ignored_layers is not None else [model.conv_out])

@@ -107,25 +107,15 @@ def build_table(mode):
 
 
 def lay_out(groups, device):
-    """Offsets as pruning._score_all_batched assigns them: (groups for ops.score_groups, idx tensor, scratch length)."""
-    out, idx_host, need = [], [], 0
+    """Offsets as pruning's own member table assigns them: (groups for ops.score_groups, idx tensor, scratch length).  A member
+    without an index list takes all n0 channels of its layer in order."""
+    table, out = pkg('pruning')._MemberTable(), []
     for members, n0 in groups:
-        ms = []
-        for m in members:
-            d = dict(w=m['w'].to(device).contiguous(), g=m['g'].to(device).contiguous(), R=m['R'], C=m['C'], T=m['T'], dim=m['dim'],
-                     mode=m['mode'], full_off=0, col_off=0, idx_off=-1)
-            if m['mode'] != 3 and m['dim'] == 1:
-                d['col_off'] = need
-                need += m['C'] * m['T']
-            else:
-                d['full_off'] = need
-                need += m['R']
-            if m['idx'] is not None:
-                d['idx_off'] = len(idx_host)
-                idx_host.extend(m['idx'])
-            ms.append(d)
+        ms = table.add([(m['w'].to(device).contiguous(), m['g'].to(device).contiguous(), m['R'], m['C'], m['T'], m['dim'], (m['mode'],),
+                         m['idx'] if m['idx'] is not None else list(range(n0))) for m in members], n0)
+        assert [d['idx_off'] >= 0 for d in ms] == [m['idx'] is not None for m in members]
         out.append((ms, n0))
-    return out, torch.tensor(idx_host, dtype=torch.int64, device=device), need
+    return out, torch.tensor(table.idx, dtype=torch.int64, device=device), table.need
 
 
 def host_scores(groups, dtype):
