@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .sweep import dist_active
+from .sweep import Pipeline, dist_active, flatten_grads
 
 CFG_SHARED_STEM = not os.environ.get('DP_NO_CFG_SHARED_STEM')
 
@@ -262,49 +262,34 @@ class _LaggedFlag:
 LDM_PIPELINES = 1            # importance steps in flight (ldm_importance_sweep, pipelines=); env DP_LDM_PIPELINES
 
 
-class _Pipe:
-    """One importance-step pipeline: engine, gradient buffer, HIP stream.  The first one is the model's own engine on the
-    caller's stream; `another()` builds a further one over the same parameters and packed operands.  `updated` orders the ONE
-    sequential piece of the pass across pipelines -- the loss test: the state update of step t is enqueued behind that of
-    step t - 1 (wait_updated / mark_updated), and `seen` is the state as it stood right after this pipeline's own update,
-    so a later step's update on the other stream cannot cancel this step's gradient."""
+class _Pipe(Pipeline):
+    """One importance-step pipeline.  The first one is the model's own engine on the caller's stream; `_Pipe.another` builds a
+    further one over the same parameters and packed operands (sweep.Pipeline).  `updated` orders the ONE sequential piece of
+    the pass across pipelines -- the loss test: the state update of step t is enqueued behind that of step t - 1
+    (wait_updated / mark_updated), and `seen` is the state as it stood right after this pipeline's own update, so a later
+    step's update on the other stream cannot cancel this step's gradient."""
 
-    def __init__(self, dev, step, stream, flat=None):
-        self.dev, self.step, self.stream, self.flat = dev, step, stream, flat
-        self.sample_engine = None if stream is None and flat is None else step.eng
-        self.on = dev.type == 'cuda'
+    def __init__(self, eng, G, flat=None, stream=None, slot=0):
+        super().__init__(eng, G, flat, stream, slot)
+        self.on = next(iter(G.values())).is_cuda
         self.updated = torch.cuda.Event() if self.on else None
         self.seen = None
-        self.started = False
         if stream is not None:                           # what exists now: uncond embedding, state, schedule tables, warm packs
             self.born = torch.cuda.Event()
             self.born.record()
-            self.packed = len(step.eng.packs._c)
-
-    @classmethod
-    def another(cls, model, schedule, first_step, dev):
-        eng = type(first_step.eng)(model.config)
-        eng.packs = first_step.eng.packs                 # frozen weights (pin_weights): one set of packed operands
-        total = sum(g.numel() for g in first_step._G.values())
-        flat2 = torch.zeros(total, dtype=torch.float32, device=dev)
-        G2, off = {}, 0
-        for n, g in first_step._G.items():
-            G2[n] = flat2[off:off + g.numel()].view_as(g)
-            off += g.numel()
-        eng.bind(first_step._P, G2)
-        eng.stream_slot = 1                               # its weight-gradient side stream is not the first engine's
-        from .engine import shared_stream
-        stream = shared_stream(dev, 'pipeline', 1) if dev.type == 'cuda' else None
-        return cls(dev, LdmSweepStep(model, schedule, first_step.global_numel, engine=eng, grads=G2), stream, flat2)
+            self.packed = len(eng.packs._c)
 
     @contextlib.contextmanager
     def scope(self):
         if self.stream is None:
             yield
             return
-        if not self.started:                             # once: every operand the first step packed lazily on the caller's
-            if len(self.step.eng.packs._c) != self.packed:             # stream is complete -- the whole first step when it packed
-                self.stream.wait_stream(torch.cuda.current_stream())   # something, else only what preceded it
+        # First use: every operand the first step packed lazily on the caller's stream is complete -- the whole first step
+        # when it packed something, else only what preceded this pipeline's birth.  (An image-sweep timestep pipeline always
+        # waits for the whole current stream.)
+        if not self.started:
+            if len(self.eng.packs._c) != self.packed:
+                self.stream.wait_stream(torch.cuda.current_stream())
             else:
                 self.stream.wait_event(self.born)
             self.started = True
@@ -322,12 +307,6 @@ class _Pipe:
         if self.on:
             self.updated.record()
         return self.seen
-
-    def fold_into(self, flat):
-        if self.stream is not None and self.started:
-            torch.cuda.current_stream().wait_stream(self.stream)
-        if self.flat is not None and (self.started or self.stream is None):
-            ops.axpby(self.flat, 1.0, flat, 1.0)
 
 
 X_T_STREAM, NOISE_STREAM = 0x7854, 0x6e73          # Philox stream ids of the two draws of a step ('xT', 'ns')
@@ -357,7 +336,6 @@ def ldm_importance_sweep(model, embedder, schedule=None, num_steps=1000, thr=0.1
     DP_LDM_SAMPLER_SHARD overrides).  The scored forward / backward always runs on the latent shard.
     Returns dict(losses [global], steps, accumulated, flat_grads, shard, sampler_rows)."""
     import torch.distributed as dist
-    from .sweep import flatten_grads
     dev = next(model.parameters()).device
     use_dist = dist_active(group)
     rank, world = (dist.get_rank(group), dist.get_world_size(group)) if use_dist else (0, 1)
@@ -394,10 +372,14 @@ def ldm_importance_sweep(model, embedder, schedule=None, num_steps=1000, thr=0.1
     rows_mode = (use_dist and shard is None and sampler_shard != 'latents' and pipelines < 2 and (world > 1 or sampler_shard == 'rows')
                  and (sampler_shard == 'rows' or rows_balance_better(n_samples, world)))
     rows = sampler_rows(n_samples, rank, world) if rows_mode else None
-    pipes = [_Pipe(dev, step, None)]
+    pipes = [_Pipe(step.eng, step._G)]
+    pipes[0].step = step
     if pipelines >= 2 and on_device:
         schedule.tables(dev)                         # on the device before a second stream is born (it waits for that moment)
-        pipes += [_Pipe.another(model, schedule, step, dev) for _ in range(pipelines - 1)]
+        for _ in range(pipelines - 1):               # every further pipeline of this pass is on stream slot 1
+            pipe = _Pipe.another(step.eng, step._P, step._G, 1, dev)
+            pipe.step = LdmSweepStep(model, schedule, step.global_numel, engine=pipe.eng, grads=pipe.G)
+            pipes.append(pipe)
 
     def draw(t):
         # rows mode: class ids and x_T of ALL n latents (every rank samples rows of latents it does not score), noise of the shard
@@ -424,7 +406,8 @@ def ldm_importance_sweep(model, embedder, schedule=None, num_steps=1000, thr=0.1
                     samples = ddim_sample_cfg_rows(model, schedule, x_T, c, uc, ddim_steps, scale, rows, group)[lo:hi].contiguous()
                     c = c[lo:hi].contiguous()            # the scored forward / backward: this rank's latents
                 else:
-                    samples = ddim_sample_cfg(model, schedule, x_T, c, uc, S=ddim_steps, scale=scale, engine=pipe.sample_engine)
+                    samples = ddim_sample_cfg(model, schedule, x_T, c, uc, S=ddim_steps, scale=scale,
+                                              engine=None if pipe is pipes[0] else pipe.eng)
                 tt = torch.full((n_loc,), t, dtype=torch.long, device=dev)
                 if on_device:
                     before = pipes[(t - 1) % len(pipes)] if (len(pipes) > 1 and t > 0) else None
@@ -450,8 +433,9 @@ def ldm_importance_sweep(model, embedder, schedule=None, num_steps=1000, thr=0.1
                 break
             step.backward()
             accumulated += 1
-    for pipe in pipes[1:]:                           # fixed order: deterministic sums
-        pipe.fold_into(flat)
+    # Fold: in fixed order (deterministic sums); the buffers die with the pass, so nothing is zeroed (HipSweepStep.finish() does)
+    for pipe in pipes[1:]:
+        pipe.fold_into(flat, axpby=ops.axpby)
     if on_device:
         st = [float(v) for v in state.cpu()]
         steps = int(st[2])

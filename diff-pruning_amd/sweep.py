@@ -67,17 +67,68 @@ class StepThrottle:
         self.i += 1
 
 
+def grad_views(like):
+    """A zeroed flat fp32 buffer and {name: view of it shaped like like[name]}: the views tile the buffer in dict order."""
+    total = sum(t.numel() for t in like.values())
+    flat = torch.zeros(total, dtype=torch.float32, device=next(iter(like.values())).device)
+    views, off = {}, 0
+    for n, t in like.items():
+        views[n] = flat[off:off + t.numel()].view_as(t)
+        off += t.numel()
+    return flat, views
+
+
 def flatten_grads(model):
     """Point every parameter's .grad at a slice of one zero-initialised flat fp32 buffer; returns the buffer."""
-    params = [p for p in model.parameters()]
-    total = sum(p.numel() for p in params)
-    flat = torch.zeros(total, dtype=torch.float32, device=params[0].device)
-    off = 0
-    for p in params:
-        n = p.numel()
-        p.grad = flat[off:off + n].view_as(p)
-        off += n
+    params = dict(model.named_parameters())
+    flat, views = grad_views(params)
+    for n, p in params.items():
+        p.grad = views[n]
     return flat
+
+
+class Pipeline:
+    """A further pipeline of a sweep: an engine over the first engine's parameters and packed operands with its own gradient
+    views `G` into its own flat buffer, on the stream of `slot` (None on a CPU device), folded into the main gradients once, at
+    the end.  `started`: work has been put on its stream.  `serial` (half-batch pipelines): run on the caller's stream instead.
+    Fields also read and written as items (`pipe['serial'] = True`, `pipe['eng']`)."""
+
+    def __init__(self, eng, G, flat=None, stream=None, slot=0):
+        self.eng, self.G, self.flat, self.stream, self.slot = eng, G, flat, stream, slot
+        self.started = self.serial = False
+
+    @classmethod
+    def another(cls, first, P, G, slot, dev):
+        """Another pipeline over the parameters `P` and the packs of the engine `first`, gradient buffer laid out like `G`."""
+        flat, G2 = grad_views(G)
+        eng = type(first)(first.cfg)
+        eng.packs = first.packs                           # frozen weights: one set of packed operands for every pipeline
+        eng.stream_slot = slot                            # its weight-gradient side stream is not the first engine's
+        eng.bind(P, G2)
+        return cls(eng, G2, flat, shared_stream(dev, 'pipeline', slot) if dev.type == 'cuda' else None, slot)
+
+    def __getitem__(self, name):
+        return getattr(self, name)
+
+    def __setitem__(self, name, value):
+        setattr(self, name, value)
+
+    def fold_into(self, flat, G=None, zero=False, axpby=None):
+        """Add this pipeline's gradients to `flat` (flat None: view by view to `G`, in dict order) on the current stream, which
+        first waits for the pipeline's; a pipeline with a stream that never started is skipped.  `axpby`: the caller's kernel
+        wrapper where that is not this module's `ops.axpby`."""
+        axpby = axpby or ops.axpby
+        if self.stream is not None:
+            if not self.started:
+                return
+            torch.cuda.current_stream().wait_stream(self.stream)
+        if flat is not None:                              # one launch over the whole buffer
+            axpby(self.flat, 1.0, flat, 1.0)
+        else:
+            for n, g in G.items():
+                axpby(self.G[n].reshape(-1), 1.0, g.reshape(-1), 1.0)
+        if zero:
+            self.flat.zero_()
 
 
 class HipSweepStep:
@@ -85,15 +136,19 @@ class HipSweepStep:
     `micro` (images): the shard is walked in micro-batches of that size within every timestep (gradients accumulate, the
     per-image loss scaling is the global one, so the result is the same sum) -- for shards whose activations would
     exceed the 2 GiB-per-tensor limit of the buffer descriptors (e.g. 256x256 images at batch >= 64 per GPU)."""
-    _graph = None
-    _replay = None
-    micro = None
-    _half = None
-    stop_state = None          # device [loss_max, stopped, steps] of the on-device Diff-Pruning early exit (taylor_sweep)
-    _tp = None
-    _tp_want = 1
-    _tp_count = 0
-    sequential = False         # True: the caller reads every step's loss before the next (host-side threshold test): one pipeline
+
+    def __new__(cls, *args, **kwargs):
+        # Everything that is not a constructor argument starts here, once -- in __new__, because the mocked-kernel and gloo tests
+        # put a CPU constructor in the place of __init__ and still run the steps below.
+        self = super().__new__(cls)
+        self.micro = None
+        self.stop_state = None     # device [loss_max, stopped, steps] of the on-device Diff-Pruning early exit (taylor_sweep)
+        self.sequential = False    # True: the caller reads every step's loss before the next (host-side threshold test): one pipeline
+        self._half = None          # the half-batch Pipeline of halves == 2
+        self._tp, self._tp_want, self._tp_count = None, 1, 0     # timestep Pipelines: made by the first call that can use them
+        self._graph = self._replay = self._dout = None
+        self._th, self.throttle_wait_s = StepThrottle(), 0.0
+        return self
 
     def __init__(self, model, scheduler, clean, noise, global_numel, loss_kind='mse', global_batch=None, halves=None,
                  timestep_pipelines=None):
@@ -124,8 +179,10 @@ class HipSweepStep:
         # default stays ONE pipeline; `halves=2` / DP_HALVES=2 remains selectable (tested: same masks, bit-reproducible).
         if halves is None:
             halves = int(os.environ.get('DP_HALVES', '1'))
-        if halves == 2 and self.B >= 2 and isinstance(self.eng, UNetEngine) and type(self.eng) is UNetEngine:
-            self._setup_second_half()
+        if halves == 2 and self.B >= 2 and type(self.eng) is UNetEngine:
+            # Dropout: the second half's images are rows B // 2 ... of the batch (a timestep pipeline's start at the main one's)
+            self._half = self._another_pipeline(1, self.B // 2)
+            self._half.started = True                     # Fold: it runs in every step, so finish() never skips it
         # Two TIMESTEPS in flight (plain Taylor only: no step depends on another).  Timesteps of odd position run through a second
         # engine -- same parameters, own context, own flat gradient buffer, own stream -- at the FULL batch, so the kernels keep
         # their size (the half-batch pipelines above lost to their smaller launches) and the two independent kernel streams fill
@@ -139,60 +196,35 @@ class HipSweepStep:
             timestep_pipelines = int(os.environ.get('DP_TIMESTEP_PIPELINES', str(TIMESTEP_PIPELINES if big else 1)))
         # created lazily by the first call that can use them (never with a threshold, micro-batches or a captured step), so a
         # sweep that cannot run two timesteps at once pays neither the second activation context nor the gradient buffer
-        self._tp = None
         self._tp_want = timestep_pipelines if (self._half is None and type(self.eng) is UNetEngine) else 1
-        self._tp_count = 0
+
+    def _another_pipeline(self, slot, n_off):
+        """Pipeline `slot` of this step (stream slot `slot`, engine.shared_stream); `n_off`: where its images start in the batch."""
+        pipe = Pipeline.another(self.eng, self._P, self._G, slot, self.clean.device)
+        pipe.eng.set_dropout(self.eng.dropout, self.eng.drop_seed, self.eng.drop_step, self.eng.drop_n_off + n_off)
+        # Construction: the main engine is bound again once the other one exists, and packs before the other stream's first read
+        self.eng.bind(self._P, self._G)
+        self.eng.prepare_packs()
+        return pipe
 
     def _make_timestep_pipelines(self):
         """The extra pipelines of `timestep_pipelines` >= 2; on an allocation failure the sweep stays on one pipeline."""
         self._tp = []
         try:
-            for _ in range(self._tp_want - 1):
-                self._setup_second_half()
-                tp, self._half = self._half, None
-                tp['eng'].set_dropout(self.eng.dropout, self.eng.drop_seed, self.eng.drop_step, self.eng.drop_n_off)
-                tp['synced'] = False
-                self._tp.append(tp)
+            for slot in range(1, self._tp_want):
+                self._tp.append(self._another_pipeline(slot, 0))
         except torch.cuda.OutOfMemoryError:
             import warnings
             warnings.warn('no memory for a second timestep pipeline (gradient buffer): sweeping with one')
-            self._half, self._tp = None, []
+            self._tp = []
         return self._tp
 
-    def _setup_second_half(self):
-        dev = self.clean.device
-        total = sum(g.numel() for g in self._G.values())
-        flat2 = torch.zeros(total, dtype=torch.float32, device=dev)
-        G2, off = {}, 0
-        for n, g in self._G.items():
-            G2[n] = flat2[off:off + g.numel()].view_as(g)
-            off += g.numel()
-        eng2 = UNetEngine(self.eng.cfg)
-        slot = 1 + len(self._tp or [])                    # pipeline k of this step: stream slot k (engine.shared_stream)
-        eng2.stream_slot = slot
-        eng2.packs = self.eng.packs                       # frozen weights: one set of packed operands for both halves
-        eng2.bind(self._P, G2)
-        eng2.set_dropout(self.eng.dropout, self.eng.drop_seed, self.eng.drop_step, self.eng.drop_n_off + self.B // 2)
-        self.eng.bind(self._P, self._G)
-        self.eng.prepare_packs()                          # packed before the second stream's first read
-        self._half = dict(eng=eng2, G=G2, flat=flat2, stream=shared_stream(dev, 'pipeline', slot), h=self.B // 2, serial=False)
-
     def finish(self):
-        """Fold the second pipeline's gradients into the parameters' .grad buffers (once per sweep)."""
-        others = [self._half] if self._half is not None else (getattr(self, '_tp', None) or [])
-        for second in others:                                  # fixed order: deterministic sums
-            if second.get('synced') is False:
-                continue                                       # a timestep pipeline that never ran (sweep with a threshold)
-            cur = torch.cuda.current_stream()
-            cur.wait_stream(second['stream'])
-            flat = self._flat_of_grads()
-            if flat is not None:                               # .grad buffers are consecutive views of one flat buffer: one launch
-                ops.axpby(second['flat'], 1.0, flat, 1.0)
-            else:
-                for n, g in self._G.items():
-                    g2 = second['G'][n]
-                    ops.axpby(g2.reshape(-1), 1.0, g.reshape(-1), 1.0)
-            second['flat'].zero_()
+        """Fold the other pipelines' gradients into the parameters' .grad buffers (once per sweep)."""
+        # Fold: a timestep pipeline that never ran (sweep with a threshold) is skipped; one launch when the .grad buffers are
+        # consecutive views of one flat buffer; the pipeline's buffer is zeroed for the next sweep.  (The LDM pass never zeroes.)
+        for pipe in [self._half] if self._half is not None else (self._tp or []):       # fixed order: deterministic sums
+            pipe.fold_into(self._flat_of_grads(), self._G, zero=True)
 
     def _flat_of_grads(self):
         """The flat buffer behind the parameters' .grad views (flatten_grads), when they tile it in order; else None."""
@@ -212,39 +244,41 @@ class HipSweepStep:
         if self._half is not None and self.micro is None:
             return self._two_half_step(t)
         if self.micro is None or self.B <= self.micro:
-            return self._micro_step(self.clean, self.noise, t)
+            return self._micro_step(slice(None), t)
         total = None
         for lo in range(0, self.B, self.micro):
             hi = min(lo + self.micro, self.B)
-            l = self._micro_step(self.clean[lo:hi], self.noise[lo:hi], t[lo:hi])
+            l = self._micro_step(slice(lo, hi), t[lo:hi])
             total = l if total is None else ops.axpby(l, 1.0, total, 1.0)
         return total
 
+    def _forward_loss(self, eng, sl, t, stop_state):
+        """noise -> forward -> loss of the images `sl` of the shard at the timesteps `t`, on `eng` and the current stream:
+        (loss, dOut).  The caller picks the stream and runs `eng.backward(dOut)` when it is due."""
+        noisy = ops.add_noise(self.clean[sl], self.noise[sl], self.acp, t)
+        out = eng.forward(noisy, t, save=True)
+        return ops.mse_fwd_bwd(out, self.noise[sl], self.gscale, self.lscale, stop_state=stop_state)
+
     def _two_half_step(self, t):
-        hf = self._half
-        h = hf['h']
+        # Half-batch step: the other stream waits for the current one, runs its half, and the current one waits for it
+        hf, h = self._half, self.B // 2
         cur = torch.cuda.current_stream()
-        s1 = cur if hf['serial'] else hf['stream']        # serial: both halves on one stream (per-kernel timing in bench.py)
+        s1 = cur if hf.serial else hf.stream              # serial: both halves on one stream (per-kernel timing in bench.py)
         s1.wait_stream(cur)
         t.record_stream(s1)
-        la = self._micro_step(self.clean[:h], self.noise[:h], t[:h])
+        la = self._micro_step(slice(0, h), t[:h])
         with torch.cuda.stream(s1):
-            eng = hf['eng']
-            noisy = ops.add_noise(self.clean[h:], self.noise[h:], self.acp, t[h:])
-            out = eng.forward(noisy, t[h:], save=True)
-            lb, dout = ops.mse_fwd_bwd(out, self.noise[h:], self.gscale, self.lscale, stop_state=self.stop_state)
-            eng.backward(dout)
+            lb, dout = self._forward_loss(hf.eng, slice(h, None), t[h:], self.stop_state)
+            hf.eng.backward(dout)
         cur.wait_stream(s1)
         lb.record_stream(cur)
         return ops.axpby(lb, 1.0, la, 1.0)
 
-    def _micro_step(self, clean, noise, t):
+    def _micro_step(self, sl, t):
         # any model(...) / model.engine() call between two sweep steps (a no-grad evaluation, the autograd bridge) re-binds
         # the engine without -- or with temporary -- gradient buffers: bind ours again
         self.eng.bind(self._P, self._G)
-        noisy = ops.add_noise(clean, noise, self.acp, t)
-        out = self.eng.forward(noisy, t, save=True)
-        loss, dout = ops.mse_fwd_bwd(out, noise, self.gscale, self.lscale, stop_state=self.stop_state)
+        loss, dout = self._forward_loss(self.eng, sl, t, self.stop_state)
         self.eng.backward(dout)
         return loss
 
@@ -255,9 +289,7 @@ class HipSweepStep:
             raise NotImplementedError('break-before-backward keeps one forward context: not combined with micro-batches')
         t = torch.full((self.B,), int(k), dtype=torch.long, device=self.clean.device)
         self.eng.bind(self._P, self._G)
-        noisy = ops.add_noise(self.clean, self.noise, self.acp, t)
-        out = self.eng.forward(noisy, t, save=True)
-        loss, self._dout = ops.mse_fwd_bwd(out, self.noise, self.gscale, self.lscale, stop_state=self.stop_state)
+        loss, self._dout = self._forward_loss(self.eng, slice(None), t, self.stop_state)
         return loss
 
     def backward_pending(self, cancel_if_stopped=False):
@@ -317,28 +349,25 @@ class HipSweepStep:
 
     def _second_pipeline_step(self, k, tp):
         """Timestep k on another pipeline's stream and engine (full batch, own gradient buffer)."""
-        if not tp['synced']:             # once: inputs, schedule table and every packed operand (also the ones the first timestep
-            tp['stream'].wait_stream(torch.cuda.current_stream())      # packed lazily on the main stream) are complete
-            tp['synced'] = True
-        with torch.cuda.stream(tp['stream']):
+        # First use: ONE wait for the current stream -- inputs, schedule table and every packed operand (also the ones the first
+        # timestep packed lazily on the main stream) are complete -- and no edge after it until finish().  (The LDM pipeline
+        # waits for the event of its birth instead, when nothing was packed since.)
+        if not tp.started:
+            tp.stream.wait_stream(torch.cuda.current_stream())
+            tp.started = True
+        with torch.cuda.stream(tp.stream):
             t = torch.full((self.B,), int(k), dtype=torch.long, device=self.clean.device)
-            eng = tp['eng']
-            noisy = ops.add_noise(self.clean, self.noise, self.acp, t)
-            out = eng.forward(noisy, t, save=True)
-            loss, dout = ops.mse_fwd_bwd(out, self.noise, self.gscale, self.lscale)
-            eng.backward(dout)
+            # no stop_state, unlike every other caller: __call__ sends a step here only while there is none, and a state on the
+            # main stream would be one this stream has no edge to
+            loss, dout = self._forward_loss(tp.eng, slice(None), t, None)
+            tp.eng.backward(dout)
         return loss
 
     def _throttle(self, stream=None):
         if self.clean.device.type != 'cuda':
             return
-        th = self.__dict__.get('_th')
-        if th is None:
-            th = self._th = StepThrottle()
-        th.mark(stream)
-        self.throttle_wait_s = th.wait_s
-
-    throttle_wait_s = 0.0
+        self._th.mark(stream)
+        self.throttle_wait_s = self._th.wait_s
 
     def __call__(self, k):
         if self._tp_want >= 2 and self.stop_state is None and self._graph is None and self.micro is None and not self.sequential:
@@ -347,7 +376,7 @@ class HipSweepStep:
             self._tp_count += 1
             if i:
                 loss = self._second_pipeline_step(k, tps[i - 1])
-                self._throttle(tps[i - 1]['stream'])
+                self._throttle(tps[i - 1].stream)
                 return loss
         if self._graph is not None:
             self._t.fill_(int(k))
@@ -431,10 +460,7 @@ def taylor_sweep(model, scheduler, clean_images, noise, num_steps=1000, thr=None
                 losses_dev = torch.zeros(num_steps, dtype=torch.float32, device=clean_images.device)
                 step_fn.stop_state = stop_state
             step_fn.capture()
-    losses = []
-    pending = []
-    loss_max = 0.0
-    steps = 0
+    losses, pending, loss_max, steps = [], [], 0.0, 0
     if two_phase and use_graph:
         raise ValueError('use_graph replays forward + backward as one unit: not available with accumulate_breaking_step=False')
     on_device = (thr is not None and device_exit and (not use_graph or stop_state is not None)
@@ -449,52 +475,37 @@ def taylor_sweep(model, scheduler, clean_images, noise, num_steps=1000, thr=None
         if losses_dev is None:
             losses_dev = torch.zeros(num_steps, dtype=torch.float32, device=dev)
         step_fn.stop_state = state
-        k = 0
-        while k < num_steps:
-            l = step_fn.forward_loss(k) if two_phase else step_fn(k)
-            if use_dist:
-                dist.all_reduce(l, group=group)
+    for k in range(num_steps):
+        l = step_fn.forward_loss(k) if two_phase else step_fn(k)
+        steps += 1
+        if use_dist and thr is not None:        # with a threshold (on the device or the host, one phase or two): every step's
+            dist.all_reduce(l, group=group)     # loss; plain Taylor: one stacked all-reduce after the sweep
+        stop = False
+        if on_device:
             ops.early_exit_update(l, thr, state, losses_dev)
             if two_phase:
                 step_fn.backward_pending(cancel_if_stopped=True)
-            k += 1
-            if k % poll_every == 0 or k == num_steps:
+            if (k + 1) % poll_every == 0 or k + 1 == num_steps:
                 t_poll = time.perf_counter()
-                stopped = float(state[1]) != 0.0            # one host sync per poll_every timesteps
+                stop = float(state[1]) != 0.0               # one host sync per poll_every timesteps
                 poll_wait += time.perf_counter() - t_poll
-                if stopped:
-                    break
+        elif thr is not None:
+            lv = float(l)                       # host sync: the reference's `if loss > loss_max` (ddpm_prune.py:104-106)
+            losses.append(lv)
+            loss_max = max(loss_max, lv)
+            stop = _f32_lt_prod(lv, loss_max, thr)
+            if two_phase and stop:
+                step_fn.discard_pending()
+            elif two_phase:
+                step_fn.backward_pending()
+        else:
+            pending.append(l)
+        if stop:
+            break
+    if on_device:
         step_fn.stop_state = None
         steps = int(float(state[2]))
         losses = [float(v) for v in losses_dev[:steps].cpu()]
-    for k in range(0 if not on_device else num_steps, num_steps):
-        if two_phase:
-            l = step_fn.forward_loss(k)
-            steps += 1
-            if use_dist:
-                dist.all_reduce(l, group=group)
-            lv = float(l)
-            losses.append(lv)
-            if lv > loss_max:
-                loss_max = lv
-            if _f32_lt_prod(lv, loss_max, thr):
-                step_fn.discard_pending()
-                break
-            step_fn.backward_pending()
-            continue
-        l = step_fn(k)
-        steps += 1
-        if use_dist and (thr is not None):
-            dist.all_reduce(l, group=group)
-        if thr is not None:
-            lv = float(l)                       # host sync: the reference's `if loss > loss_max` (ddpm_prune.py:104-106)
-            losses.append(lv)
-            if lv > loss_max:
-                loss_max = lv
-            if _f32_lt_prod(lv, loss_max, thr):
-                break
-        else:
-            pending.append(l)
     if timings is not None:
         # host time spent ENQUEUEING: the waits inside the polls of the on-device early exit (which drain the queue) are not part
         # of it -- with them the figure is just the step time (bedroom-256: 58.07 of a 58.08 ms step in round 3)

@@ -822,6 +822,42 @@ def _cpu_step_init(self, model, scheduler, clean, noise, global_numel, loss_kind
     self.acp = scheduler.alphas_cumprod
 
 
+def test_gradient_views_and_further_pipelines(mocked, monkeypatch):
+    """sweep.grad_views tiles one zeroed flat buffer with parameter-shaped views in parameter order; flatten_grads lays the
+    .grad buffers out so that HipSweepStep._flat_of_grads finds the buffer (and finds none once a .grad is a tensor of its
+    own); Pipeline.another builds engines that share the first one's packs, on their own slots and buffers."""
+    sweep = pkg('sweep')
+    monkeypatch.setattr(sweep.HipSweepStep, '__init__', _cpu_step_init)
+    model = _cpu_model(gc.TINY_CFG, 5)
+    params = dict(model.named_parameters())
+    flat, views = sweep.grad_views(params)
+    assert flat.dtype == torch.float32 and flat.dim() == 1 and flat.numel() == sum(p.numel() for p in params.values())
+    assert not flat.any() and list(views) == list(params)
+    off = flat.data_ptr()
+    for n, p in params.items():
+        assert views[n].shape == p.shape and views[n].is_contiguous() and views[n].data_ptr() == off, n
+        off += 4 * p.numel()
+    assert off == flat.data_ptr() + 4 * flat.numel()
+
+    base = sweep.flatten_grads(model)
+    clean, noise = torch.zeros(2, 3, 16, 16), torch.zeros(2, 3, 16, 16)
+    sched = pkg('diffusion').DDPMScheduler()
+    step = sweep.HipSweepStep(model, sched, clean, noise, clean.numel())
+    assert step._flat_of_grads() is base and not base.any()
+    G, name = step._G, list(params)[3]
+    params[name].grad = torch.zeros_like(params[name])
+    assert sweep.HipSweepStep(model, sched, clean, noise, clean.numel())._flat_of_grads() is None
+
+    one, two = (sweep.Pipeline.another(step.eng, step._P, G, slot, clean.device) for slot in (1, 2))
+    assert one.eng.packs is two.eng.packs is step.eng.packs and type(one.eng) is type(step.eng)
+    assert (one.slot, one.eng.stream_slot, two.slot, two.eng.stream_slot) == (1, 1, 2, 2)
+    assert one.stream is None and not one.started and not one['serial']
+    assert one.eng.P is step._P and one.eng.G is one.G and [v.shape for v in one.G.values()] == [g.shape for g in G.values()]
+    ends = sorted((b.data_ptr(), b.data_ptr() + 4 * b.numel()) for b in (base, one.flat, two.flat))
+    assert all(a[1] <= b[0] for a, b in zip(ends, ends[1:]))
+    assert all(one.G[n]._base is one.flat and two.G[n]._base is two.flat for n in G)
+
+
 def test_prune_flow_on_mocked_kernels_matches_reference_masks(mocked, monkeypatch):
     """sweep -> TaylorImportance -> MagnitudePruner.step(interactive) -> group.prune() end to end (host logic +
     mocked kernels) reproduces the reference's masks for the tiny UNet."""

@@ -1054,6 +1054,31 @@ def test_two_half_batch_pipelines_match_single_pipeline(report):
     assert e2['steps'] == e1['steps'] and np.allclose(e2['losses'], e1['losses'], rtol=1e-6)
 
 
+def test_serial_half_batch_pipeline_gives_the_same_bits():
+    """What bench.py's instrumented() does to a half-batch step -- `_half['serial'] = True`, no weight-gradient side stream on
+    `_half['eng']` -- puts both halves on the caller's stream: the same kernels on the same inputs in the same order per buffer,
+    so the flat gradients and the losses are those of the two-stream run bit for bit."""
+    sweep, sched = pkg('sweep'), pkg('diffusion').DDPMScheduler()
+    clean, noise = (x.to(DEV) for x in _inputs(2, 16, 7, 8))
+
+    def run(serial):
+        model = make_model(gc.TINY_CFG, 5)
+        flat = sweep.flatten_grads(model)
+        step = sweep.HipSweepStep(model, sched, clean, noise, clean.numel(), 'mse', 2, halves=2)
+        assert isinstance(step._half, sweep.Pipeline) and not step._half['serial']
+        step.eng.overlap_wgrad = False
+        if serial:
+            step._half['serial'] = True
+            step._half['eng'].overlap_wgrad = False
+        res = sweep.taylor_sweep(model, sched, clean, noise, num_steps=2, step_fn=step, flat_grads=flat)
+        torch.cuda.synchronize()
+        return flat, res['losses']
+
+    (g_two, l_two), (g_one, l_one) = run(False), run(True)
+    assert float(g_two.abs().max()) > 0 and len(l_two) == 2
+    assert torch.equal(g_two, g_one) and l_two == l_one
+
+
 def test_fid_inception_forward_and_statistics(report):
     """Row f3: the FID Inception network on the HIP kernels (BatchNorm folded, one conv + bias + ReLU launch per BasicConv2d,
     branches written into channel slices) against the oracle's PyTorch restatement with seeded weights (torchvision is absent:
