@@ -172,6 +172,7 @@ SIGNATURES = {
     'dp_adamw_ema': [_vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _vp],
     'dp_embedding_bwd': [_vp, _vp, _i, _i, _vp, _vp],
     'dp_ema_update': [_vp, _vp, _ll, _f, _vp],
+    'dp_fold_sum': [_vp, C.POINTER(C.c_void_p), _i, _ll, _vp],
     'dp_adam_ema_dev': [_vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _f, _f, _f, _f, _vp],
     'dp_ddim_step': [_vp, _vp, _vp, _f, _f, _f, _i, _f, _vp, _ll, _vp],
     'dp_ddpm_step': [_vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, _ll, _vp],

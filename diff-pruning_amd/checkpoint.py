@@ -50,6 +50,8 @@ def save_pruned(model, directory, pruning_history):
     meta = dict(format_version=FORMAT_VERSION, model_class=type(model).__name__, config=_config_dict(model),
                 pruning_history=[[n, bool(o), [int(i) for i in ix]] for n, o, ix in pruning_history],
                 shapes={k: list(v.shape) for k, v in sd.items()}, num_parameters=int(sum(v.numel() for v in sd.values())))
+    if getattr(model, 'attention_scale_from_width', False):          # an original-DDPM model: its attention rescales with the prune
+        meta['attention_scale_from_width'] = True
     with open(os.path.join(directory, META), 'w') as f:
         json.dump(meta, f)
     return meta
@@ -63,6 +65,8 @@ def load_pruned(directory, device=None):
     if meta.get('format_version') != FORMAT_VERSION:
         raise ValueError('unsupported pruned-checkpoint format %r' % (meta.get('format_version'),))
     model = _build(meta['model_class'], meta['config'])
+    if meta.get('attention_scale_from_width'):
+        model.attention_scale_from_width = True
     pruning.DependencyGraph(model).load_pruning_history(meta['pruning_history'])
     pruning.fix_static_attributes(model)
     sd = load_file(os.path.join(directory, WEIGHTS))

@@ -187,6 +187,11 @@ class UNetEngine:
         # 16.1 / 12.0; batch 64: 24.4 / 25.4; LDM UNet, 6 latents: 51.1 / 55.8.  overlap_wgrad = None (default) decides per
         # backward pass from the work of the step (images x pixels x base width >= OVERLAP_MIN_WORK); True / False force it.
         self._nograd = False
+        # Attention scale.  Diffusers fixes `Attention.scale = dim_head ** -0.5` at construction (attention_processor.py:85-86): a
+        # pruned q / k keeps the scale of the unpruned width -- `attn_scale` below, the default.  The original-DDPM model
+        # (ddpm_exp/models/diffusion.py AttnBlock: `w_ * int(c) ** -0.5`, c = q.shape[1]) takes the width AT RUN TIME, i.e. the
+        # pruned one.  Equal until a model is pruned; set from UNet2DModel.attention_scale_from_width by model.engine().
+        self.scale_from_q_width = False
         self.overlap_wgrad = False if os.environ.get('DP_NO_OVERLAP') else (True if os.environ.get('DP_OVERLAP') else None)
         self._overlap_now = True
         self._side, self._side_dev = None, None
@@ -683,6 +688,8 @@ class UNetEngine:
             k = self._conv(pre + '.to_k', n, None, _SPEC1)
             v = self._conv(pre + '.to_v', n, None, _SPEC1)
         inner = q.shape[1]
+        if self.scale_from_q_width:                   # original-DDPM models (UNet2DModel.attention_scale_from_width)
+            scale = float(inner // heads) ** -0.5
         # heads: channel-major tokens make head_to_batch_dim (attention_processor.py:283-305) a view: head h owns the
         # contiguous channel rows [h*d, (h+1)*d) of every image -> batch index n*heads + h
         Z, d = N * heads, inner // heads

@@ -1822,6 +1822,22 @@ def ema_update(shadow, p_, decay):
     return shadow
 
 
+FOLD_SUM_MAX_SRCS = 4
+
+
+def fold_sum(out, srcs):
+    """out = ((srcs[0] + srcs[1]) + srcs[2]) + srcs[3] over flat fp32 buffers (dp_fold_sum, csrc/stage.hip): 1 .. 4 sources, plain
+    fp32 adds in that order -- the bits a copy followed by `axpby(src, 1.0, out, 1.0)` per further source gives -- in one pass and
+    without writing a source.  `out` must not overlap a source (DpHipError).  The pointers go by value: no device-side table."""
+    srcs = list(srcs)
+    n = out.numel()
+    for t in [out] + srcs:
+        assert t.is_cuda and t.dtype == _f32 and t.is_contiguous() and t.numel() == n, 'fold_sum: flat contiguous fp32 device buffers'
+    ptrs = (C.c_void_p * max(len(srcs), 1))(*[t.data_ptr() for t in srcs])
+    L.check(_lib().dp_fold_sum(_p(out), ptrs, len(srcs), n, _stream()), 'dp_fold_sum')
+    return out
+
+
 EMBEDDING_BWD_MAX_ROWS = 4096
 
 

@@ -104,6 +104,7 @@ class Pipeline:
         eng = type(first)(first.cfg)
         eng.packs = first.packs                           # frozen weights: one set of packed operands for every pipeline
         eng.stream_slot = slot                            # its weight-gradient side stream is not the first engine's
+        eng.scale_from_q_width = first.scale_from_q_width
         eng.bind(P, G2)
         return cls(eng, G2, flat, shared_stream(dev, 'pipeline', slot) if dev.type == 'cuda' else None, slot)
 
@@ -225,6 +226,39 @@ class HipSweepStep:
         # consecutive views of one flat buffer; the pipeline's buffer is zeroed for the next sweep.  (The LDM pass never zeroes.)
         for pipe in [self._half] if self._half is not None else (self._tp or []):       # fixed order: deterministic sums
             pipe.fold_into(self._flat_of_grads(), self._G, zero=True)
+
+    def snapshot(self, out=None):
+        """The gradients accumulated so far as finish() would leave them -- the main buffer plus the buffer of every started
+        pipeline, in finish()'s order -- written to `out` (a flat fp32 buffer laid out like flatten_grads', made when None)
+        through ops.fold_sum.  Nothing of the sweep changes: no buffer is written, no counter, flag or dropout state moves, and
+        the sweep that goes on is bit for bit the one that was never looked at.
+        Before the fold the current stream waits for every started pipeline's stream.  That is all finish() relies on as well:
+        every backward ends in UNetEngine._end_backward, whose _join_side makes the stream the backward ran on wait for the
+        engine's weight-gradient side stream, so a pipeline's stream is behind everything its timesteps put on either.  After
+        the fold every started pipeline's stream waits for the current one: its next `+=` does not race the fold's read."""
+        pipes = [self._half] if self._half is not None else (self._tp or [])
+        pipes = [p for p in pipes if p.stream is None or p.started]
+        if len(pipes) + 1 > ops.FOLD_SUM_MAX_SRCS:
+            raise NotImplementedError('snapshot() folds at most %d gradient buffers in one pass' % ops.FOLD_SUM_MAX_SRCS)
+        total = sum(g.numel() for g in self._G.values())
+        if out is None:
+            out = torch.empty(total, dtype=torch.float32, device=self.clean.device)
+        assert out.dim() == 1 and out.numel() == total and out.dtype == torch.float32 and out.is_contiguous()
+        streams = [p.stream for p in pipes if p.stream is not None]
+        cur = torch.cuda.current_stream() if streams else None
+        for s in streams:
+            cur.wait_stream(s)
+        flat = self._flat_of_grads()
+        if flat is not None:                              # one launch over the whole buffer
+            ops.fold_sum(out, [flat] + [p.flat for p in pipes])
+        else:
+            off = 0
+            for n, g in self._G.items():
+                ops.fold_sum(out[off:off + g.numel()], [g.reshape(-1)] + [p.G[n].reshape(-1) for p in pipes])
+                off += g.numel()
+        for s in streams:
+            s.wait_stream(cur)
+        return out
 
     def _flat_of_grads(self):
         """The flat buffer behind the parameters' .grad views (flatten_grads), when they tile it in order; else None."""
@@ -399,10 +433,44 @@ def _f32_lt_prod(loss, loss_max, thr):
     return bool(np.float32(loss) < np.float32(loss_max) * np.float32(thr))
 
 
+class _StagedStep:
+    """`step_fn` of a staged sweep (taylor_sweep(stages=...)): before timestep k it takes the snapshot of stage k, when k is one
+    -- the gradients of the timesteps 0 .. k - 1 -- into row i of `bufs`, then runs the timestep.  `take()` after the last timestep
+    serves the stage num_steps.  A step with a `snapshot` method (HipSweepStep) folds its pipelines' buffers without touching them;
+    any other step is snapshotted as a copy of `flat_grads`."""
+
+    def __init__(self, step, stages, bufs, flat_grads):
+        self.step, self.stages, self.bufs, self.flat_grads, self.i = step, stages, bufs, flat_grads, 0
+
+    def take(self):
+        if hasattr(self.step, 'snapshot'):
+            self.step.snapshot(out=self.bufs[self.i])
+        else:
+            self.bufs[self.i].copy_(self.flat_grads)
+        self.i += 1
+
+    def __call__(self, k):
+        if self.i < len(self.stages) and self.stages[self.i] == k:
+            self.take()
+        return self.step(k)
+
+
 def taylor_sweep(model, scheduler, clean_images, noise, num_steps=1000, thr=None, loss_kind='mse', group=None,
                  step_fn=None, flat_grads=None, reduce_grads=True, use_graph=None, micro_batch=None,
-                 accumulate_breaking_step=True, device_exit=True, poll_every=8, timings=None):
+                 accumulate_breaking_step=True, device_exit=True, poll_every=8, timings=None, stages=None):
     """Runs the sweep; returns dict(losses=[python floats of the GLOBAL loss per executed step], steps=int).
+
+    stages (plain Taylor only; a sorted list of distinct integers in [0, num_steps]): the stage study's snapshots
+    (ddpm_exp/prune_ssim.py:236-267 runs a fresh s-step sweep per stage s; the gradient after s timesteps is a prefix of this
+    sweep's).  The result gains stage_grads = {s: flat fp32 tensor laid out like flatten_grads' buffer}: the gradients accumulated
+    over the timesteps 0 .. s - 1, bit for bit those of a fresh `num_steps=s` sweep in the same mode, taken between timestep
+    s - 1 and timestep s without disturbing the sweep (HipSweepStep.snapshot), whose losses and final gradients are bit for bit
+    those of the sweep without `stages`.  The snapshots are COLLECTED during the sweep and CONSUMED after it -- nothing else runs
+    on the device between two timesteps (another model's forwards between two replays of a captured timestep could grow the
+    shared split-K workspace the captured nodes point into) -- so all of them are alive at the end: len(stages) x 4 B x
+    parameters (CIFAR, 20 stages: 20 x 143 MB), allocated in one piece before the first timestep.  Under a process group they are
+    local sums during the sweep and, with reduce_grads, all-reduced after it, one after another, before the final gradient's
+    exchange.  None: nothing of this runs.
 
     thr=None: plain Taylor.  thr=x: Diff-Pruning early exit.  accumulate_breaking_step=True is ddpm_prune.py:102-106
     (backward, then the threshold test); False is the ddpm_exp flavour (ddpm_exp/prune.py:249-256: test, break, else
@@ -425,6 +493,12 @@ def taylor_sweep(model, scheduler, clean_images, noise, num_steps=1000, thr=None
     done with them) and 'allreduce_s' (the gradient exchange alone; only then is the exchange followed by a device sync)."""
     import time
     import torch.distributed as dist
+    if stages is not None:
+        stages = [int(s) for s in stages]
+        if thr is not None:
+            raise ValueError('stages: the stage study is a plain Taylor sweep, it has no early exit (thr must be None)')
+        if any(b <= a for a, b in zip(stages, stages[1:])) or any(not 0 <= s <= num_steps for s in stages):
+            raise ValueError('stages must be sorted, distinct and within [0, num_steps]: %r' % (stages,))
     t_start = time.perf_counter()
     poll_wait = 0.0
     throttle_wait0 = float(getattr(step_fn, 'throttle_wait_s', 0.0))
@@ -475,6 +549,17 @@ def taylor_sweep(model, scheduler, clean_images, noise, num_steps=1000, thr=None
         if losses_dev is None:
             losses_dev = torch.zeros(num_steps, dtype=torch.float32, device=dev)
         step_fn.stop_state = state
+    if stages is not None:
+        # every snapshot's memory before the first timestep: a sweep that cannot hold them fails here, not at a stage boundary
+        if hasattr(step_fn, 'snapshot'):
+            n_flat = sum(g.numel() for g in step_fn._G.values())
+        elif flat_grads is not None:
+            n_flat = flat_grads.numel()
+        else:
+            raise ValueError('stages: a step_fn without a snapshot() method is snapshotted through flat_grads, which is None')
+        staged = _StagedStep(step_fn, stages, torch.empty((len(stages), n_flat), dtype=torch.float32, device=clean_images.device),
+                             flat_grads)
+        inner_step, step_fn = step_fn, staged             # the loop below calls the staged step
     for k in range(num_steps):
         l = step_fn.forward_loss(k) if two_phase else step_fn(k)
         steps += 1
@@ -502,6 +587,11 @@ def taylor_sweep(model, scheduler, clean_images, noise, num_steps=1000, thr=None
             pending.append(l)
         if stop:
             break
+    if stages is not None:
+        step_fn = inner_step
+        if staged.i < len(stages):                        # the stage num_steps: after the last timestep, before finish()
+            staged.take()
+        assert staged.i == len(stages)
     if on_device:
         step_fn.stop_state = None
         steps = int(float(state[2]))
@@ -523,12 +613,18 @@ def taylor_sweep(model, scheduler, clean_images, noise, num_steps=1000, thr=None
     if timings is not None:
         torch.cuda.synchronize()
         timings['sweep_s'] = time.perf_counter() - t_start
+    if stages is not None and use_dist and reduce_grads:
+        for i in range(len(stages)):                  # local sums until here: one exchange per snapshot, in stage order
+            dist.all_reduce(staged.bufs[i], group=group)
     if use_dist and reduce_grads and flat_grads is not None:
         dist.all_reduce(flat_grads, group=group)      # the one exchange step of the sweep (sum of per-shard grads)
         if timings is not None:
             torch.cuda.synchronize()
             timings['allreduce_s'] = time.perf_counter() - t_start - timings['sweep_s']
-    return dict(losses=losses, steps=steps, global_batch=B_global)
+    res = dict(losses=losses, steps=steps, global_batch=B_global)
+    if stages is not None:
+        res['stage_grads'] = {s: staged.bufs[i] for i, s in enumerate(stages)}
+    return res
 
 
 def prune_model(model, pruning_ratio=0.3, importance=None, ignored_layers=None, channel_groups=None, global_pruning=False,

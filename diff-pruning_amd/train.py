@@ -192,6 +192,7 @@ def load_teacher(src, device, ch=None, ch_mult=None, num_res_blocks=None, attn_r
                                                           in_channels, out_ch)
         model = UNet2DModel(**cfg)
         model.load_state_dict(checkpoint.convert_ddpm_original(sd), strict=True)
+        model.attention_scale_from_width = True            # AttnBlock's `int(c) ** -0.5`: the same number until the model is pruned
     model = model.to(device).eval()
     for p in model.parameters():
         p.requires_grad_(False)

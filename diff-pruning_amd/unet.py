@@ -131,6 +131,13 @@ _DEFAULTS = dict(
 class UNet2DModel(nn.Module):
     """Construction order follows unet_2d.py:84-217, so `state_dict()` key order matches the reference."""
 
+    # True: the attention logits are scaled by the q width AT RUN TIME, as the original-DDPM model does (ddpm_exp/models/
+    # diffusion.py AttnBlock: `w_ * int(c) ** -0.5`), so a pruned q / k rescales; False: Diffusers' `Attention.scale`, fixed at
+    # construction.  The two agree until the model is pruned.  Not a config key (Diffusers has none): an attribute, set by
+    # train.load_teacher for original-DDPM checkpoints (set it yourself on a model built otherwise), carried by whole-module pickles,
+    # save_pruned / load_pruned and stage_study.prune_at_stage.
+    attention_scale_from_width = False
+
     def __init__(self, **kwargs):
         super().__init__()
         cfg = dict(_DEFAULTS)
@@ -261,6 +268,7 @@ class UNet2DModel(nn.Module):
             self._engine = UNetEngine(self.config)
         params = {n: p.detach() for n, p in self.named_parameters()}
         self._engine.packs.rebind()           # in-place weight writes (EMAModel.copy_to / restore) are invisible to the cache
+        self._engine.scale_from_q_width = bool(self.attention_scale_from_width)
         self._engine.bind(params, None)
         self._engine.set_dropout(self.dropout_table() if self.training else None, getattr(self, 'dropout_seed', 0),
                                  getattr(self, '_dropout_step', 0))

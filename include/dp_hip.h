@@ -449,6 +449,13 @@ int dp_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long 
  * accumulation window that end without an optimizer step.  16-byte accesses when both pointers are 16-byte aligned, 4-byte
  * accesses for the n % 4 tail and for unaligned views; any n (long long indexing, grid-stride under dp_adamw_ema's cap). */
 int dp_ema_update(float* s, const float* p, long long n, float one_minus_decay, void* stream);
+/* The stage study's snapshot (csrc/stage.hip): out[i] = ((srcs[0][i] + srcs[1][i]) + srcs[2][i]) + srcs[3][i], i < n, for k = 1 .. 4
+ * sources: plain fp32 adds in exactly that order, the sum a chain of dp_axpby(src, 1, out, 1) forms.  `srcs`: k device pointers in
+ * HOST memory; they are passed on by value in the kernel arguments (nothing is staged, nothing has to outlive the call).  No source
+ * is written.  hipErrorInvalidValue when `out` overlaps a source, k is out of range or a pointer is null; n <= 0 is a no-op.
+ * 16-byte accesses when `out` and every source are 16-byte aligned and n >= 4, 4-byte accesses for the n % 4 tail and for
+ * unaligned views; any n (long long indexing, grid-stride beyond 4096 blocks: dp_ema_update's rule). */
+int dp_fold_sum(float* out, const float* const* srcs, int k, long long n, void* stream);
 /* Gradient of an embedding lookup: dW[ids[b], :] += dctx[b, :] for b = 0 .. B-1 (B <= 4096), the rows of a repeated id added in
  * ascending b -- bitwise reproducible, no float atomics.  ids: int64, every id in [0, rows of dW) (checked by the caller). */
 int dp_embedding_bwd(const long long* ids, const float* dctx, int B, int D, float* dW, void* stream);
