@@ -94,6 +94,10 @@ class ColsumItem(C.Structure):
                 ('woff', C.c_int), ('accumulate', C.c_int), ('ld', C.c_int)]
 
 
+class DpmSolverCoef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sigma_s', 'alpha_s', 'kx', 'k0', 'k1', 'k2', 'ir0', 'ir1', 'q', 'iq')]
+
+
 _vp, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, LL
 _dr = C.POINTER(Dropout)
 
@@ -179,6 +183,7 @@ SIGNATURES = {
     'dp_denoise_step': [_vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _ll, _vp],
     'dp_image_to_u8': [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp],
     'dp_cfg_denoise_step': [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp],
+    'dp_dpm_solver_step': [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(DpmSolverCoef), _vp, _vp, _ll, _vp],
     'dp_dropout_apply': [_vp, _ll, _vp, _ll, _i, _ll, _dr, _vp],
     'dp_dropout_mask': [_vp, _ll, _ll, _dr, _vp],
     'dp_layernorm_fwd': [_vp, _ll, _vp, _vp, _i, _i, _i, _f, _vp, _ll, _vp, _vp],

@@ -269,6 +269,223 @@ class DDIMScheduler(_SchedulerBase):
 
 
 @dataclass
+class SchedulerOutput:
+    prev_sample: torch.Tensor
+
+
+def _betas_for_alpha_bar(num_diffusion_timesteps, max_beta=0.999):
+    """The `squaredcos_cap_v2` table (scheduling_dpmsolver_multistep.py:29-55): Python doubles, one cast to fp32 at the end."""
+    import math
+
+    def alpha_bar(s):
+        return math.cos((s + 0.008) / 1.008 * math.pi / 2) ** 2
+    n = num_diffusion_timesteps
+    return torch.tensor([min(1 - alpha_bar((i + 1) / n) / alpha_bar(i / n), max_beta) for i in range(n)], dtype=torch.float32)
+
+
+def _rounded_once(fn, t):
+    """fn(t) of an fp32 CPU tensor as the correctly rounded fp32 value: evaluated in fp64, rounded to fp32 once.  torch's fp32
+    sqrt / log / exp on the CPU come from the host's vector math library: they are within an ulp, not correctly rounded, and two
+    hosts with the same torch build return different last bits (measured: two x86 hosts of different vendors disagree on 5 of the 1000
+    alpha_t entries).  The solver differences lambda values that are close together, so one such bit moves a third-order update by
+    ten times its fp32 rounding error.  Rounded once from fp64, the tables and the per-step scalars are the same on every host."""
+    return fn(t.double()).float()
+
+
+class DPMSolverMultistepScheduler(_SchedulerBase):
+    """scheduling_dpmsolver_multistep.py:58-707, the deterministic multistep DPM-Solver / DPM-Solver++ of orders 1 .. 3 for epsilon
+    models.  The tables and every per-step scalar are 0-d fp32 torch arithmetic on the CPU in the reference's operation order
+    (:420-423, :466-473, :557-572), with sqrt, log and exp correctly rounded (_rounded_once: the reference's bits on a host whose
+    math library rounds them correctly, and the same bits on every host); the per-element work of a step -- convert_model_output
+    and the update -- is ONE launch of dp_dpm_solver_step (ops.dpm_solver_step).  The timesteps are kept as a host list beside the `timesteps` tensor, so `step`
+    reads nothing back from the device.  The history is a ring of `solver_order` device buffers that the steps write in turn.
+    Not carried (NotImplementedError): the SDE variants, dynamic thresholding, `sample` / `v_prediction` models, models that
+    predict a variance, `trained_betas`."""
+    order = 1
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'solver_order',
+                    'prediction_type', 'thresholding', 'dynamic_thresholding_ratio', 'sample_max_value', 'algorithm_type',
+                    'solver_type', 'lower_order_final', 'use_karras_sigmas', 'lambda_min_clipped', 'variance_type')
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', trained_betas=None,
+                 solver_order=2, prediction_type='epsilon', thresholding=False, dynamic_thresholding_ratio=0.995,
+                 sample_max_value=1.0, algorithm_type='dpmsolver++', solver_type='midpoint', lower_order_final=True,
+                 use_karras_sigmas=False, lambda_min_clipped=-float('inf'), variance_type=None):
+        if trained_betas is not None:
+            raise NotImplementedError('trained_betas is not on the hot path')
+        if prediction_type != 'epsilon':
+            raise NotImplementedError('only epsilon prediction is on the hot path')
+        if thresholding:
+            raise NotImplementedError('dynamic thresholding is not on the hot path')
+        if variance_type in ('learned', 'learned_range'):
+            raise NotImplementedError('learned-variance models are not part of this path')
+        if algorithm_type == 'deis':                                  # :188-198: the two rewrites of register_to_config
+            algorithm_type = 'dpmsolver++'
+        if algorithm_type not in ('dpmsolver', 'dpmsolver++'):
+            raise NotImplementedError('algorithm_type %s is not implemented (the SDE variants are left out)' % algorithm_type)
+        if solver_type in ('logrho', 'bh1', 'bh2'):
+            solver_type = 'midpoint'
+        if solver_type not in ('midpoint', 'heun'):
+            raise NotImplementedError('solver_type %s is not implemented' % solver_type)
+        if int(solver_order) < 1:
+            raise ValueError('solver_order must be at least 1')
+        self.config = SimpleNamespace(
+            num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+            trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
+            dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value,
+            algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final,
+            use_karras_sigmas=use_karras_sigmas, lambda_min_clipped=lambda_min_clipped, variance_type=variance_type)
+        if beta_schedule == 'squaredcos_cap_v2':
+            self.betas = _betas_for_alpha_bar(num_train_timesteps)
+        else:
+            self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.alpha_t = _rounded_once(torch.sqrt, self.alphas_cumprod)
+        self.sigma_t = _rounded_once(torch.sqrt, 1 - self.alphas_cumprod)
+        self.lambda_t = _rounded_once(torch.log, self.alpha_t) - _rounded_once(torch.log, self.sigma_t)
+        self.init_noise_sigma = 1.0
+        self._acp_dev = {}
+        self.num_inference_steps = None
+        self._set_list(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
+        self.use_karras_sigmas = use_karras_sigmas
+
+    @classmethod
+    def from_config(cls, config):
+        d = vars(config) if not isinstance(config, dict) else config
+        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+    def scale_model_input(self, sample, *args, **kwargs):
+        return sample
+
+    def _set_list(self, ts, device=None):
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._ts = [int(v) for v in ts]                               # the host's copy: what `step` looks timesteps up in
+        self._index = {}
+        for i, v in enumerate(self._ts):
+            self._index.setdefault(v, i)
+        self.model_outputs = [None] * self.config.solver_order        # newest last, as the reference keeps them
+        self.lower_order_nums = 0
+
+    def _sigma_to_t(self, sigma, log_sigmas):
+        """:285-306 for one sigma: the fractional index at which log sigma lies between two neighbours of the table."""
+        log_sigma = np.log(sigma)
+        dists = log_sigma - log_sigmas[:, np.newaxis]
+        low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+        high_idx = low_idx + 1
+        low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+        w = np.clip((low - log_sigma) / (low - high), 0, 1)
+        t = (1 - w) * low_idx + w * high_idx
+        return t.reshape(sigma.shape)
+
+    def _convert_to_karras(self, in_sigmas, num_inference_steps):
+        """:309-320, Karras et al. (2022) with rho = 7."""
+        sigma_min, sigma_max = in_sigmas[-1].item(), in_sigmas[0].item()
+        rho = 7.0
+        ramp = np.linspace(0, 1, num_inference_steps)
+        min_inv_rho, max_inv_rho = sigma_min ** (1 / rho), sigma_max ** (1 / rho)
+        return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** rho
+
+    def set_timesteps(self, num_inference_steps=None, device=None):
+        """:208-247: the lambda_min_clipped search, the rounded linspace (or the Karras sigmas mapped back to timesteps), duplicates
+        removed in order of appearance, the history reset."""
+        clipped_idx = int(torch.searchsorted(torch.flip(self.lambda_t, [0]), self.config.lambda_min_clipped))
+        ts = (np.linspace(0, self.config.num_train_timesteps - 1 - clipped_idx, num_inference_steps + 1)
+              .round()[::-1][:-1].copy().astype(np.int64))
+        if self.use_karras_sigmas:
+            sigmas = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+            log_sigmas = np.log(sigmas)
+            sigmas = self._convert_to_karras(in_sigmas=sigmas, num_inference_steps=num_inference_steps)
+            ts = np.array([self._sigma_to_t(sigma, log_sigmas) for sigma in sigmas]).round()
+            ts = np.flip(ts).copy().astype(np.int64)
+        _, unique_indices = np.unique(ts, return_index=True)
+        ts = ts[np.sort(unique_indices)]
+        self._set_list(ts, device)
+        self.num_inference_steps = len(ts)
+
+    def step_coefs(self, order, timestep, prev_timestep, s1=None, s2=None):
+        """The fp32 scalars of one update as ops.dpm_solver_step names them, formed as :351, :420-427, :466-501 and :557-588 form
+        them.  `timestep` = s0, the step's own; s1 / s2: the two timesteps before it (orders 2 / 3)."""
+        t, s0 = prev_timestep, timestep
+        plus = self.config.algorithm_type == 'dpmsolver++'
+        heun = self.config.solver_type == 'heun'
+        lambda_t, lambda_s0 = self.lambda_t[t], self.lambda_t[s0]
+        alpha_t, alpha_s0 = self.alpha_t[t], self.alpha_t[s0]
+        sigma_t, sigma_s0 = self.sigma_t[t], self.sigma_t[s0]
+        h = lambda_t - lambda_s0
+
+        def exp(v):
+            return _rounded_once(torch.exp, v)
+        c = dict(sigma_s=sigma_s0, alpha_s=alpha_s0)
+        if plus:
+            c['kx'] = sigma_t / sigma_s0
+            c['k0'] = alpha_t * (exp(-h) - 1.0)
+        else:
+            c['kx'] = alpha_t / alpha_s0
+            c['k0'] = sigma_t * (exp(h) - 1.0)
+        if order >= 2:
+            h_0 = lambda_s0 - self.lambda_t[s1]
+            r0 = h_0 / h
+            c['ir0'] = 1.0 / r0
+            if order == 2 and not heun:
+                c['k1'] = 0.5 * c['k0']
+            elif plus:                                                # the reference ADDS this term: k1 is its negative
+                c['k1'] = -(alpha_t * ((exp(-h) - 1.0) / h + 1.0))
+            else:
+                c['k1'] = sigma_t * ((exp(h) - 1.0) / h - 1.0)
+        if order == 3:
+            h_1 = self.lambda_t[s1] - self.lambda_t[s2]
+            r1 = h_1 / h
+            c['ir1'] = 1.0 / r1
+            c['q'] = r0 / (r0 + r1)
+            c['iq'] = 1.0 / (r0 + r1)
+            if plus:
+                c['k2'] = alpha_t * ((exp(-h) - 1.0 + h) / h ** 2 - 0.5)
+            else:
+                c['k2'] = sigma_t * ((exp(h) - 1.0 - h) / h ** 2 - 0.5)
+        return {k: float(v) for k, v in c.items()}
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True):
+        """:591-667.  The order is the reference's choice (solver_order, the lower_order_nums warm-up, lower_order_final /
+        lower_order_second below 15 steps); exactly one launch, nothing read back."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if model_output.shape[1] != sample.shape[1]:
+            raise NotImplementedError('learned-variance models are not part of this path')
+        ts = self._ts
+        last = len(ts) - 1
+        t = int(timestep)
+        i = self._index.get(t, last)
+        prev_t = 0 if i == last else ts[i + 1]
+        final = i == last and self.config.lower_order_final and len(ts) < 15
+        second = i == last - 1 and self.config.lower_order_final and len(ts) < 15
+        so = self.config.solver_order
+        if so == 1 or self.lower_order_nums < 1 or final:
+            order = 1
+        elif so == 2 or self.lower_order_nums < 2 or second:
+            order = 2
+        else:
+            order = 3
+        coef = self.step_coefs(order, t, prev_t, ts[i - 1] if order >= 2 else None, ts[i - 2] if order == 3 else None)
+        sample = sample.contiguous()
+        hist = self.model_outputs
+        buf = hist[0]                                                 # the oldest buffer of the ring takes this step's m0
+        if buf is None or buf.shape != sample.shape or buf.device != sample.device:
+            buf = torch.empty_like(sample)
+        prev, m0 = ops.dpm_solver_step(sample, model_output.contiguous(), coef, order=order,
+                                       data_pred=self.config.algorithm_type == 'dpmsolver++',
+                                       m1=hist[-1] if order >= 2 else None, m2=hist[-2] if order == 3 else None, m0_out=buf)
+        self.model_outputs = hist[1:] + [m0]
+        if self.lower_order_nums < so:
+            self.lower_order_nums += 1
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
+@dataclass
 class ImagePipelineOutput:
     images: object
 

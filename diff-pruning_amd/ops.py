@@ -1961,6 +1961,40 @@ def cfg_denoise_step(x, e, coef, scale=None, order=0, hist=(), z=None, temperatu
     return out
 
 
+DPM_SOLVER_MAX_BLOCKS = 4096         # DP_DPM_SOLVER_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
+DPM_SOLVER_COEF = ('sigma_s', 'alpha_s', 'kx', 'k0', 'k1', 'k2', 'ir0', 'ir1', 'q', 'iq')
+
+
+def dpm_solver_step(x, e, coef, order=1, data_pred=True, m1=None, m2=None, out=None, m0_out=None):
+    """One step of the multistep DPM-Solver (dp_dpm_solver_step, csrc/dpm_solver.hip) over flat fp32 data.  `coef`: the host's fp32
+    scalars by name (DPM_SOLVER_COEF; one an order / algorithm does not read may be left out):
+    m0 = (x - sigma_s e) / alpha_s (data_pred, dpmsolver++) | e (dpmsolver);  order 1: x' = kx x - k0 m0;
+    order 2: D1 = ir0 (m0 - m1), x' = (kx x - k0 m0) - k1 D1;  order 3: D10 = ir0 (m0 - m1), D11 = ir1 (m1 - m2), d = D10 - D11,
+    D1 = D10 + q d, D2 = iq d, x' = ((kx x - k0 m0) - k1 D1) - k2 D2.  `m1` / `m2`: the previous converted output and the one
+    before it, read from order 2 / 3 on.  `out` may be `x`; `m0_out` may be `m1` or `m2` (the oldest buffer of the caller's ring);
+    no other buffer may be shared.  Returns (out, m0_out)."""
+    n = x.numel()
+    assert order in (1, 2, 3)
+    assert x.dtype == _f32 and e.dtype == _f32 and x.is_contiguous() and e.is_contiguous() and e.numel() == n
+    hist = [m1, m2][:order - 1]
+    assert all(h is not None and h.dtype == _f32 and h.is_contiguous() and h.numel() == n for h in hist), 'dpm_solver_step: history below the order'
+    if out is None:
+        out = torch.empty_like(x)
+    if m0_out is None:
+        m0_out = torch.empty_like(x)
+    for o in (out, m0_out):
+        assert o.dtype == _f32 and o.is_contiguous() and o.numel() == n
+    assert out.data_ptr() not in [e.data_ptr(), m0_out.data_ptr()] + [h.data_ptr() for h in hist]
+    assert m0_out.data_ptr() not in (x.data_ptr(), e.data_ptr())
+    unknown = set(coef) - set(DPM_SOLVER_COEF)
+    assert not unknown, unknown
+    c = L.DpmSolverCoef(**{k: float(v) for k, v in coef.items()})
+    h = [_p(t) for t in hist] + [None] * (2 - len(hist))
+    L.check(_lib().dp_dpm_solver_step(_p(x), _p(e), h[0], h[1], int(order), 1 if data_pred else 0, C.byref(c), _p(out), _p(m0_out),
+                                      n, _stream()), 'dp_dpm_solver_step')
+    return out, m0_out
+
+
 # --------------------------------------------------------------------------------------------------
 # LDM transformer-block glue (channel-major tokens [N, C, H, W] == [N][C][T])
 # --------------------------------------------------------------------------------------------------

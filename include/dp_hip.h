@@ -512,6 +512,33 @@ int dp_cfg_denoise_step(const float* x, const float* e_u, const float* e_c, floa
                         const float* h3, float s1m, float sqrt_a_t, float sqrt_a_prev, float c_dir, float sigma, float temperature,
                         const float* z, float* next, float* x0_out, float* eg_out, long long n, void* stream);
 
+/* One step of the multistep DPM-Solver (csrc/dpm_solver.hip; diffusers/schedulers/scheduling_dpmsolver_multistep.py:346-395 epsilon
+ * prediction, :420-442, :466-501, :557-589) over n fp32 elements, one pass, in the reference's operation order:
+ *   m0 = data_pred ? (x - sigma_s * e) / alpha_s : e              dpmsolver++ (data prediction) | dpmsolver (noise prediction)
+ *   order 1:  x' = kx * x - k0 * m0
+ *   order 2:  D1 = ir0 * (m0 - m1);                                          x' = (kx * x - k0 * m0) - k1 * D1
+ *   order 3:  D10 = ir0 * (m0 - m1); D11 = ir1 * (m1 - m2); d = D10 - D11;
+ *             D1 = D10 + q * d; D2 = iq * d;                                 x' = ((kx * x - k0 * m0) - k1 * D1) - k2 * D2
+ * every operation rounded separately, a true division; the scalars are the host's 0-d fp32 arithmetic on the alpha_t / sigma_t /
+ * lambda_t tables (ir0 = 1 / r0, ir1 = 1 / r1, q = r0 / (r0 + r1), iq = 1 / (r0 + r1)); where the reference ADDS c * D1 (heun, the
+ * third-order dpmsolver++) the host passes k1 = -c, which gives the same bits.  Fields an order / algorithm does not read are ignored.
+ * m1 (the previous converted output) and m2 (the one before) may be NULL below their order.  m0_out, the converted output of this
+ * step, is always written (for dpmsolver it is a copy of e: the history owns its buffers).
+ * Aliases: `x_next` may be `x` itself, and `m0_out` may be `m1` or `m2` itself -- the oldest buffer of a ring of solver_order history
+ * buffers that this very step still reads: each lane reads every input of its elements before it writes any of them, and no
+ * other lane touches them.  Any other overlap between an output and another buffer is hipErrorInvalidValue, as are a null required
+ * pointer and an order outside 1 .. 3; n <= 0 is a no-op.
+ * 16-byte accesses between a scalar head and tail when all pointers in use share one alignment modulo 16, 4-byte accesses
+ * otherwise; any n (long long indexing, grid-stride beyond DP_DPM_SOLVER_MAX_BLOCKS blocks of 256 lanes). */
+#define DP_DPM_SOLVER_MAX_BLOCKS 4096
+typedef struct dp_dpm_solver_coef {
+    float sigma_s, alpha_s;             /* convert (data_pred only) */
+    float kx, k0, k1, k2;               /* the update's coefficients */
+    float ir0, ir1, q, iq;              /* the difference quotients of orders 2 and 3 */
+} dp_dpm_solver_coef;
+int dp_dpm_solver_step(const float* x, const float* e, const float* m1, const float* m2, int order, int data_pred,
+                       const dp_dpm_solver_coef* coef, float* x_next, float* m0_out, long long n, void* stream);
+
 /* ---- LDM (CompVis) transformer-block glue on channel-major tokens x[n][c][t]  (ldm_exp/ldm/modules/attention.py) ---- */
 /* LayerNorm over the C channels of every token (attention.py:200-212 norm1/2/3); stats[(n*T+t)*2+{0,1}] = {mean, rstd}. */
 int dp_layernorm_fwd(const float* x, long long x_img_stride, const float* gamma, const float* beta, int N, int C, int T,
