@@ -73,6 +73,15 @@ class ScoreEntry(C.Structure):
     _fields_ = [('m', ScoreMember), ('score_off', LL), ('n0', C.c_int), ('_pad', C.c_int)]
 
 
+class MagMember(C.Structure):
+    _fields_ = [('w', C.c_void_p), ('R', C.c_int), ('C', C.c_int), ('T', C.c_int), ('dim', C.c_int), ('n0', C.c_int),
+                ('blk0', C.c_int), ('fold', C.c_int), ('_pad', C.c_int), ('idx_off', LL), ('row_off', LL)]
+
+
+class MagGroup(C.Structure):
+    _fields_ = [('row_off', LL), ('score_off', LL), ('n0', C.c_int), ('members', C.c_int)]
+
+
 class PackItem(C.Structure):
     _fields_ = [('W', C.c_void_p), ('dst', C.c_void_p), ('Co', C.c_int), ('Ci', C.c_int), ('taps', C.c_int), ('mode', C.c_int),
                 ('ld', C.c_int), ('blk0', C.c_int), ('nblk', C.c_int), ('_pad', C.c_int)]
@@ -169,6 +178,9 @@ SIGNATURES = {
     'dp_score_groups': [C.POINTER(ScoreEntry), _i, _vp, _vp, _ll, _vp, _ll, _vp, _ll, _vp],
     'dp_select_smallest_workspace': [_ll, _i],
     'dp_select_smallest': [_vp, _ll, C.POINTER(LL), _i, _ll, _vp, _ll, _vp, _vp, _vp],
+    'dp_magnitude_max_width': [],
+    'dp_magnitude_rows': [C.POINTER(MagMember), _i, _vp, _vp, _ll, _f, _i, _vp, _ll, _vp],
+    'dp_magnitude_finish': [C.POINTER(MagGroup), _i, _vp, _vp, _ll, _i, _i, _i, _vp, _ll, _vp],
     'dp_sumsq_partials': [_vp, _ll, _vp, _i, _vp],
     'dp_clip_coef': [_vp, _i, _f, _vp, _vp, _vp],
     'dp_adam_ema': [_vp, _vp, _vp, _vp, _vp, _ll, _vp, _f, _f, _f, _f, _f, _f, _f, _vp],

@@ -1746,6 +1746,53 @@ def select_smallest(scores, offsets, k, raw=False):
     return (thres, idx, out) if raw else (thres, idx)
 
 
+MAGNITUDE_REDUCTIONS = {'sum': 0, 'mean': 1, 'max': 2, 'prod': 3, 'first': 4}
+MAGNITUDE_NORMALIZERS = {None: 0, 'sum': 1, 'standarization': 2, 'mean': 3, 'max': 4, 'gaussian': 5}
+MAGNITUDE_LAMP = {None: 0, 'vendored': 1, 'paper': 2}
+MAGNITUDE_MAX_WIDTH = 4096      # csrc/magnitude.hip MG_MAX_WIDTH (= dp_magnitude_max_width()): the LDS the LAMP sort of a group needs
+
+
+def magnitude_rows(members, idx_dev, p, root, rows):
+    """sum |w|^p (root: to the power 1 / p) per channel of every member of every group in ONE launch (include/dp_hip.h
+    dp_magnitude_rows).  members: dicts(w, R, C, T, dim, n0, idx_off, row_off[, fold]); idx_dev: int64 device tensor with the index
+    lists (or None); member i's n0 values land at rows[row_off ...]; fold > 1: value j sums `fold` consecutive entries of the list."""
+    n = len(members)
+    assert rows.is_cuda and rows.dtype == _f32 and rows.is_contiguous(), 'magnitude_rows takes device tensors (no CPU path)'
+    assert idx_dev is None or (idx_dev.is_cuda and idx_dev.dtype == torch.int64 and idx_dev.is_contiguous())
+    arr = (L.MagMember * max(n, 1))()
+    for a, m in zip(arr, members):
+        w = m['w']
+        assert w.is_cuda and w.dtype == _f32 and w.is_contiguous() and w.numel() == m['R'] * m['C'] * m['T'], \
+            'member view does not cover its tensor'
+        a.w, a.R, a.C, a.T, a.dim, a.n0 = w.data_ptr(), m['R'], m['C'], m['T'], m['dim'], m['n0']
+        a.idx_off, a.row_off, a.fold = m['idx_off'], m['row_off'], m.get('fold', 1)
+    table = torch.empty(max(n, 1) * C.sizeof(L.MagMember), dtype=torch.uint8, device=rows.device)
+    L.check(_lib().dp_magnitude_rows(arr, n, _p(table), _p(idx_dev), 0 if idx_dev is None else idx_dev.numel(), float(p),
+                                     1 if root else 0, _p(rows), rows.numel(), _stream()), 'dp_magnitude_rows')
+    rows._dp_table = (arr, table)             # the host table outlives the asynchronous copy, the device one the kernel
+    return rows
+
+
+def magnitude_finish(groups, rows, reduction, normalizer, lamp, scores):
+    """Member reduction, normalisation and (lamp: None / 'vendored' / 'paper') the LAMP score of every group in ONE launch, one
+    workgroup per group (dp_magnitude_finish).  groups: (row_off, n0, members) each; group i's scores land at scores[sum of the
+    earlier n0 ...].  A group wider than MAGNITUDE_MAX_WIDTH is refused (DpHipError, code 1)."""
+    n = len(groups)
+    assert rows.is_cuda and scores.is_cuda and rows.dtype == scores.dtype == _f32 and rows.is_contiguous() and scores.is_contiguous(), \
+        'magnitude_finish takes device tensors (no CPU path)'
+    arr = (L.MagGroup * max(n, 1))()
+    off = 0
+    for a, (row_off, n0, members) in zip(arr, groups):
+        a.row_off, a.score_off, a.n0, a.members = row_off, off, n0, members
+        off += n0
+    table = torch.empty(max(n, 1) * C.sizeof(L.MagGroup), dtype=torch.uint8, device=rows.device)
+    L.check(_lib().dp_magnitude_finish(arr, n, _p(table), _p(rows), rows.numel(), MAGNITUDE_REDUCTIONS[reduction],
+                                       MAGNITUDE_NORMALIZERS[normalizer], MAGNITUDE_LAMP[lamp], _p(scores), scores.numel(), _stream()),
+            'dp_magnitude_finish')
+    scores._dp_table = (arr, table)
+    return scores
+
+
 def gather_add(src, idx_long, dst):
     """dst[i] += src[idx[i]]"""
     assert idx_long.dtype == torch.int64 and idx_long.numel() == dst.numel()

@@ -1,7 +1,8 @@
 """Importance criteria, group pruner and channel-slicing functions with the `torch_pruning` call surface.
 
 Mirrors the part of (vendored) torch_pruning the reference's prune scripts use:
-  importance.TaylorImportance / MagnitudeImportance / RandomImportance   importance.py:11-16,59-126,221-225,332-434
+  importance.TaylorImportance / MagnitudeImportance / RandomImportance   importance.py:11-16,18-126,221-225,332-434
+  importance.LAMPImportance                                              importance.py:154-219
   pruner.MagnitudePruner (= MetaPruner).step(interactive) / prune_local  pruner/algorithms/metapruner.py:11-254
   MetaPruner(global_pruning=True) / prune_global                         pruner/algorithms/metapruner.py:126-133,256-297
   Group.prune()                                                          dependency.py:157-185
@@ -18,6 +19,8 @@ the same bits: member by member (ops.wg_reduce, then ops.axpby / ops.gather_add)
 every group in one launch pair (ops.score_groups, csrc/prune_global.hip).  The two batched routes lay their member table out with
 the same function (`_MemberTable.add`); every route ends in the same `_finish`.  The argsort over the <= 1024 scores of a group and
 the bookkeeping of the slicing are host work; global pruning selects on the device (ops.select_smallest).
+The data-free criteria beyond the default configuration (MagnitudeImportance with another p, reduction or normaliser, LAMPImportance)
+keep one row per member instead of a member sum and score through csrc/magnitude.hip (ops.magnitude_rows, ops.magnitude_finish).
 
 `TaylorImportance.__call__(group, ch_groups=1)` accepts both this module's groups and groups produced by a real
 `torch_pruning.DependencyGraph` (items `(dep, idxs)` with `dep.target.module` / `dep.handler`), so it can be handed
@@ -562,7 +565,8 @@ class TaylorImportance(_Criterion):
                            (importance.py:412-418) -> default True for multivariable=None.  The pip criterion of that
                            era only had a BatchNorm branch (prune_batchnorm_out_channels), GroupNorm members matched no
                            branch and added nothing -> default False for the multivariable modes (recalled, unpinned).
-    `sweep.prune_model` defaults to the vendored ('sum_sq') criterion: the only one pinned by reference outputs."""
+    `sweep.prune_model` defaults to the vendored ('sum_sq') criterion: the only one pinned by reference outputs.
+    Of `group_reduction` and `normalizer` this class honours only 'mean' (any other value leaves the member sum as it is)."""
     group_batched = True
 
     def __init__(self, group_reduction='mean', normalizer='mean', multivariable=None, groupnorm_term=None):
@@ -603,21 +607,192 @@ class FisherImportance(_Criterion):
     gn_modes = (_F_SQ,)
 
 
+_REDUCTIONS = ('sum', 'mean', 'max', 'prod', 'first')
+_NORMALIZERS = (None, 'sum', 'standarization', 'mean', 'max', 'gaussian')        # the reference's spellings
+
+
 class MagnitudeImportance(_Criterion):
-    """importance.py:59-126: sum |w|^p per conv / linear member (GroupNorm members carry no term: the vendored class only
-    matches BatchNorm), mean over members, divided by its mean.  p = 2 runs on the fused reduction with g := w: |w*w| = |w|^2."""
+    """importance.py:18-126: sum |w|^p per conv / linear member (GroupNorm members carry no term: the vendored class only
+    matches BatchNorm; members whose length differs from the first term's are dropped), `group_reduction` over the members
+    ('sum' | 'mean' | 'max' | 'prod' | 'first'), then `normalizer` (None | 'sum' | 'standarization' | 'mean' | 'max' | 'gaussian' |
+    a callable applied to each group's device tensor).  Any p > 0.  Divisions are the IEEE ones: an all-zero group under 'mean'
+    scores NaN, as it does there.
+
+    The configuration (2, 'mean', 'mean') runs where it always ran: the fused reduction with g := w (|w*w| = |w|^2) and the
+    core's mean finish.  Every other one runs on csrc/magnitude.hip: one member launch (ops.magnitude_rows) and one finish launch
+    (ops.magnitude_finish) for ALL groups handed to `score_all` (for the one group of `__call__`), no device-to-host read.
+    DP_NO_PRUNE_BATCH, host tensors, a callable normaliser or a group wider than ops.MAGNITUDE_MAX_WIDTH take the reference's
+    expressions in torch on the device the weights are on, group by group."""
     conv_modes = (_F_ABS,)
     gn_modes = ()
     mean_finish = True
+    root = False              # members are (sum |w|^p)^(1/p)
+    lamp = None               # None | 'vendored' | 'paper'
+    sort_indices = True       # importance.py:65 sorts every index list of the group in place
+    length_filter = True      # importance.py:118-122
 
     def __init__(self, p=2, group_reduction='mean', normalizer='mean'):
         super().__init__(group_reduction, normalizer)
-        if p != 2:
-            raise NotImplementedError('MagnitudeImportance: only p = 2 (the reference default) is built')
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not p > 0:
+            raise ValueError('%s: p must be a number > 0, got %r' % (type(self).__name__, p))
+        if group_reduction is None:
+            raise ValueError('group_reduction=None leaves one row per member: no pruner can rank that')
+        if group_reduction not in _REDUCTIONS:
+            raise NotImplementedError('group_reduction %r (known: %s)' % (group_reduction, ', '.join(_REDUCTIONS)))
+        if not callable(normalizer) and normalizer not in _NORMALIZERS:
+            raise NotImplementedError('normalizer %r (known: %s, or a callable)' % (normalizer, ', '.join(map(str, _NORMALIZERS))))
         self.p = p
+        self._held = None
 
     def _grad(self, layer):
         return layer.weight.data
+
+    @property
+    def _present_path(self):
+        return type(self) is MagnitudeImportance and self.p == 2 and self.group_reduction == 'mean' and self.normalizer == 'mean'
+
+    @property
+    def scores_stay_on_device(self):
+        """prune_global keeps this criterion's scores where they are (its records hold device slices)."""
+        return not self._present_path
+
+    def _mag_members(self, group):
+        """-> (n0, [(w, R, C, T, dim, idxs)]) of the members that carry a term, or None.  len(idxs) is n0, or for an in-channel
+        member of LAMPImportance a multiple of it (`_kernel_scores` / `_torch_score` fold it)."""
+        members, kinds = [], []
+        for dep, idxs in group:
+            if self.sort_indices:
+                idxs.sort()
+            kind = _member_kind(dep)
+            if kind not in ('out', 'in'):
+                continue
+            layer = dep.target.module
+            w = layer.weight.data
+            dim = 0 if kind == 'out' else 1
+            if getattr(layer, 'transposed', False):        # ConvTranspose: weight [Cin, Cout, k, k]
+                dim = 1 - dim
+            T = 1
+            for v in w.shape[2:]:
+                T *= v
+            R, Cc = w.shape[0], w.shape[1] if w.dim() > 1 else 1
+            if len(idxs) and (min(idxs) < 0 or max(idxs) >= (Cc if dim else R)):
+                raise IndexError('group member index outside its layer (%d channels)' % (Cc if dim else R))
+            members.append((w, R, Cc, T, dim, idxs))
+            kinds.append(kind)
+        if not members:
+            return None
+        n0 = len(members[0][5])
+        if self.length_filter:
+            members = [m for m in members if len(m[5]) == n0]
+        elif any(len(m[5]) != n0 and (k != 'in' or n0 == 0 or len(m[5]) % n0 or not m[5]) for m, k in zip(members, kinds)):
+            # importance.py:188-195 views an in-channel member of k * n0 channels as [n0, k, .]; anything else fails in view / torch.stack
+            raise RuntimeError('%s: the members of the group rooted at %s differ in length (%s)' % (
+                type(self).__name__, getattr(group[0][0].target, 'name', '?'), sorted({len(m[5]) for m in members})))
+        return n0, members
+
+    def _on_kernels(self, live):
+        """Per group of `live`: whether the kernels take it (a group above the cap goes to torch on its own, the rest stay batched)."""
+        if not PRUNE_BATCH or not hasattr(ops, 'magnitude_rows') or callable(self.normalizer):
+            return [False] * len(live)
+        dev = live[0][1][0][0].device
+        if dev.type != 'cuda' and not getattr(ops, 'IS_MOCK', False):
+            return [False] * len(live)
+        return [n0 <= ops.MAGNITUDE_MAX_WIDTH and all(m[0].device == dev and m[0].dtype == torch.float32 and m[0].is_contiguous() for m in ms)
+                for n0, ms in live]
+
+    def _kernel_scores(self, live):
+        """The member table and the group table of every group in `live`; two launches; -> one score view per group."""
+        members, groups, idx, row = [], [], [], 0
+        dev = live[0][1][0][0].device
+        for n0, ms in live:
+            groups.append((row, n0, len(ms)))
+            for w, R, Cc, T, dim, idxs in ms:
+                idx_off = -1
+                if not ((Cc if dim else R) == n0 == len(idxs) and all(i == j for j, i in enumerate(idxs))):
+                    idx_off = len(idx)
+                    idx.extend(idxs)
+                members.append(dict(w=w, R=R, C=Cc, T=T, dim=dim, n0=n0, idx_off=idx_off, row_off=row, fold=len(idxs) // n0))
+                row += n0
+        rows = torch.empty(row, dtype=torch.float32, device=dev)
+        scores = torch.empty(sum(n0 for n0, _ in live), dtype=torch.float32, device=dev)
+        idx_dev = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev) if idx else None
+        ops.magnitude_rows(members, idx_dev, self.p, self.root, rows)
+        ops.magnitude_finish(groups, rows, self.group_reduction, self.normalizer, self.lamp, scores)
+        self._held = (rows, scores, idx_dev)          # the launchers' tables live on these until the next call
+        out, off = [], 0
+        for n0, _ in live:
+            out.append(scores[off:off + n0])
+            off += n0
+        return out
+
+    def _torch_score(self, n0, ms):
+        """importance.py:59-126 / :161-219 in torch, in the dtype and on the device of the weights."""
+        rows = []
+        for w, R, Cc, T, dim, idxs in ms:
+            m = w.reshape(R, Cc * T) if dim == 0 else w.reshape(R, Cc, T).transpose(0, 1).reshape(Cc, R * T)
+            m = m[torch.as_tensor(idxs, dtype=torch.long, device=w.device)]
+            if len(idxs) != n0:                            # importance.py:188-195: k consecutive channels of the list make one
+                m = m.reshape(n0, -1)
+            rows.append(torch.norm(m, dim=1, p=self.p) if self.root else m.abs().pow(self.p).sum(1))
+        imp, red, norm = torch.stack(rows, dim=0), self.group_reduction, self.normalizer
+        imp = {'sum': lambda: imp.sum(dim=0), 'mean': lambda: imp.mean(dim=0), 'max': lambda: imp.max(dim=0)[0],
+               'prod': lambda: torch.prod(imp, dim=0), 'first': lambda: imp[0]}[red]()
+        if callable(norm):
+            imp = norm(imp)
+        elif norm is not None:
+            imp = {'sum': lambda: imp / imp.sum(), 'standarization': lambda: (imp - imp.min()) / (imp.max() - imp.min() + 1e-8),
+                   'mean': lambda: imp / imp.mean(), 'max': lambda: imp / imp.max(),
+                   'gaussian': lambda: (imp - imp.mean()) / (imp.std() + 1e-8)}[norm]()
+        if self.lamp is None:
+            return imp
+        a = torch.argsort(imp, dim=0, descending=True, stable=True)
+        q = imp[a]
+        q = q / torch.cumsum(q, dim=0)
+        if self.lamp == 'vendored':
+            return q[a]
+        out = torch.empty_like(q)
+        out[a] = q
+        return out
+
+    def _score(self, groups):
+        per = [self._mag_members(g) for g in groups]
+        live = [x for x in per if x is not None]
+        if not live:
+            return [None] * len(groups)
+        taken = self._on_kernels(live)
+        batched = iter(self._kernel_scores([x for x, t in zip(live, taken) if t]) if any(taken) else ())
+        got = iter([next(batched) if t else self._torch_score(n0, ms) for (n0, ms), t in zip(live, taken)])
+        return [None if x is None else next(got) for x in per]
+
+    @torch.no_grad()
+    def __call__(self, group, ch_groups=1):
+        if self._present_path:
+            return super().__call__(group, ch_groups)
+        return self._score([group])[0]
+
+    @torch.no_grad()
+    def score_all(self, groups, ch_groups=None):
+        if self._present_path:
+            return super().score_all(groups, ch_groups)
+        return self._score(groups)
+
+
+class LAMPImportance(MagnitudeImportance):
+    """importance.py:154-219: members are torch.norm(., p) per channel = (sum |w|^p)^(1/p), the same reduction and normaliser,
+    then `lamp`: with a = the descending argsort of the scores and q = sorted / cumsum(sorted), the vendored code returns q[a]
+    (`torch.arange(n)[a]` is a itself, not its inverse) -- the default, because masks are pinned to the reference; paper_order=True
+    scatters with the true inverse (out[a[k]] = q[k]), the score of arXiv 2010.07611.  Ties sort by ascending channel.  As there, the
+    index lists are not sorted and no member is dropped.  An in-channel member that holds the group's channels k times over (both
+    halves of a concatenation come from the group) is viewed as [n0, k, .], k consecutive entries of its list to a channel, as
+    importance.py:188-195 does; any other difference in length raises RuntimeError naming the root layer (there: torch.stack / view)."""
+    root = True
+    sort_indices = False
+    length_filter = False
+
+    def __init__(self, p=2, group_reduction='mean', normalizer='mean', paper_order=False):
+        super().__init__(p, group_reduction, normalizer)
+        self.paper_order = bool(paper_order)
+        self.lamp = 'paper' if paper_order else 'vendored'
 
 
 class RandomImportance(Importance):
@@ -629,7 +804,8 @@ class RandomImportance(Importance):
 importance = SimpleNamespace(Importance=Importance, TaylorImportance=TaylorImportance,
                              FullTaylorImportance=FullTaylorImportance, AbsTaylorImportance=AbsTaylorImportance,
                              FisherImportance=FisherImportance,
-                             MagnitudeImportance=MagnitudeImportance, RandomImportance=RandomImportance)
+                             MagnitudeImportance=MagnitudeImportance, LAMPImportance=LAMPImportance,
+                             RandomImportance=RandomImportance)
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -871,9 +1047,12 @@ class MetaPruner:
         offsets = [0]
         for r in ranked:
             offsets.append(offsets[-1] + len(r[-1]))
-        imp_host = imp.detach().float().cpu()
         on_device = imp.is_cuda or getattr(ops, 'IS_MOCK', False)
-        if PRUNE_BATCH and hasattr(ops, 'select_smallest') and on_device and all(a < b for a, b in zip(offsets, offsets[1:])):
+        select = PRUNE_BATCH and hasattr(ops, 'select_smallest') and on_device and all(a < b for a, b in zip(offsets, offsets[1:]))
+        # a criterion that scores on the device without a read (csrc/magnitude.hip) keeps its scores there: the selection's one copy is the only one
+        stay = select and getattr(self.importance, 'scores_stay_on_device', False)
+        imp_host = imp.detach() if stay else imp.detach().float().cpu()
+        if select:
             thres, picked = ops.select_smallest(imp.detach().float().contiguous(), offsets, n_pruned)
         else:
             topk_imp, _ = torch.topk(imp_host, k=n_pruned, largest=False)

@@ -421,6 +421,39 @@ long long dp_select_smallest_workspace(long long n, int groups);
 int dp_select_smallest(const float* scores, long long n, const long long* group_off, int groups, long long k, void* work,
                        long long work_bytes, int* out_dev, int* out_host, void* stream);
 
+/* The data-free magnitude criteria (importance.py:18-126 MagnitudeImportance, :154-219 LAMPImportance; csrc/magnitude.hip), every
+ * group of the network in one launch pair.
+ * dp_magnitude_rows: member i views its weight as [R][C][T]; rows[row_off + j], j < n0, = sum |w|^p over the other dimensions of
+ * channel idx[idx_off + j] (idx_off < 0: channel j) along `dim`; root != 0: that sum to the power 1 / p (torch.norm(., p)).
+ * fold > 1 (needs an index list of n0 * fold entries): value j sums the channels idx[idx_off + j * fold .. + fold), in list order,
+ * before the root -- the `view` of importance.py:188-195 for an in-channel member that holds its group's channels `fold` times.
+ * p == 1 and p == 2 take |w| and w * w, any other p > 0 the device powf.  `members` (host, n of them) is checked against idx_len
+ * and rows_len, gets blk0 filled in and is copied to table_dev (device, n entries), from where the kernel reads it; a channel
+ * index outside the layer is clamped into it.  Two calls give the same bits.
+ * dp_magnitude_finish: group i owns `members` rows of n0 floats, adjacent from rows[row_off] in member order, and
+ * scores[score_off .. score_off + n0); the groups tile scores[0 .. n_scores) in table order.  One workgroup per group:
+ *   reduction   0 sum, 1 mean, 2 max, 3 prod, 4 first -- over the rows, in member order;
+ *   normalizer  0 none, 1 / sum, 2 (x - min) / (max - min + 1e-8), 3 / mean, 4 / max, 5 (x - mean) / (std + 1e-8), std unbiased,
+ *               two passes; IEEE divisions (an all-zero group under 3 gives NaN); min / max return NaN when the group holds one;
+ *   lamp        0 off; else a = descending argsort (ties by ascending channel), q = sorted / inclusive scan of sorted (the scan in
+ *               index order, as torch.cumsum on the host); 1: scores[j] = q[a[j]] (importance.py:211-219 as vendored),
+ *               2: scores[a[k]] = q[k] (the paper's order).
+ * n0 > dp_magnitude_max_width() (the LDS the sort needs) is refused with hipErrorInvalidValue. */
+typedef struct dp_mag_member {
+    const float* w;
+    int R, C, T, dim, n0, blk0, fold, _pad;
+    long long idx_off, row_off;
+} dp_mag_member;
+typedef struct dp_mag_group {
+    long long row_off, score_off;
+    int n0, members;
+} dp_mag_group;
+int dp_magnitude_max_width(void);
+int dp_magnitude_rows(dp_mag_member* members, int n, dp_mag_member* table_dev, const int64_t* idx, long long idx_len,
+                      float p, int root, float* rows, long long rows_len, void* stream);
+int dp_magnitude_finish(const dp_mag_group* groups, int n, dp_mag_group* table_dev, const float* rows, long long rows_len,
+                        int reduction, int normalizer, int lamp, float* scores, long long n_scores, void* stream);
+
 /* Fused finetune update over flat buffers (ddpm_train.py:462-469, training_utils.py:201-216):
  *   g *= clip_coef (clip_coef read from device: min(1, max_norm/(norm+1e-6)));  Adam;  EMA with constant decay. */
 int dp_sumsq_partials(const float* x, long long n, float* partial, int nblocks, void* stream);
