@@ -107,6 +107,11 @@ class DpmSolverCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sigma_s', 'alpha_s', 'kx', 'k0', 'k1', 'k2', 'ir0', 'ir1', 'q', 'iq')]
 
 
+class UniPCCoef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sigma_s', 'alpha_s', 'c_cx', 'c_c0', 'c_cB', 'c_rk1', 'c_rk2', 'c_rho1', 'c_rho2', 'c_rho_last',
+                                         'p_cx', 'p_c0', 'p_cB', 'p_rk1', 'p_rk2', 'p_rho1', 'p_rho2')]
+
+
 _vp, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, LL
 _dr = C.POINTER(Dropout)
 
@@ -196,6 +201,7 @@ SIGNATURES = {
     'dp_image_to_u8': [_vp, _ll, _i, _i, _i, _i, _i, _vp, _vp],
     'dp_cfg_denoise_step': [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp],
     'dp_dpm_solver_step': [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(DpmSolverCoef), _vp, _vp, _ll, _vp],
+    'dp_unipc_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(UniPCCoef), _vp, _vp, _vp, _ll, _vp],
     'dp_dropout_apply': [_vp, _ll, _vp, _ll, _i, _ll, _dr, _vp],
     'dp_dropout_mask': [_vp, _ll, _ll, _dr, _vp],
     'dp_layernorm_fwd': [_vp, _ll, _vp, _vp, _i, _i, _i, _f, _vp, _ll, _vp, _vp],

@@ -60,6 +60,21 @@ class _SchedulerBase:
         self.init_noise_sigma = 1.0
         self._acp_dev = {}
 
+    def _init_solver_tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule):
+        """The alpha_t / sigma_t / lambda_t tables of the multistep solvers (scheduling_dpmsolver_multistep.py:158-176,
+        scheduling_unipc_multistep.py:144-167), sqrt and log correctly rounded (_rounded_once)."""
+        if beta_schedule == 'squaredcos_cap_v2':
+            self.betas = _betas_for_alpha_bar(num_train_timesteps)
+        else:
+            self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.alpha_t = _rounded_once(torch.sqrt, self.alphas_cumprod)
+        self.sigma_t = _rounded_once(torch.sqrt, 1 - self.alphas_cumprod)
+        self.lambda_t = _rounded_once(torch.log, self.alpha_t) - _rounded_once(torch.log, self.sigma_t)
+        self.init_noise_sigma = 1.0
+        self._acp_dev = {}
+
     def _acp_on(self, device):
         t = self._acp_dev.get(device)
         if t is None:
@@ -334,17 +349,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
             dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value,
             algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final,
             use_karras_sigmas=use_karras_sigmas, lambda_min_clipped=lambda_min_clipped, variance_type=variance_type)
-        if beta_schedule == 'squaredcos_cap_v2':
-            self.betas = _betas_for_alpha_bar(num_train_timesteps)
-        else:
-            self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.alpha_t = _rounded_once(torch.sqrt, self.alphas_cumprod)
-        self.sigma_t = _rounded_once(torch.sqrt, 1 - self.alphas_cumprod)
-        self.lambda_t = _rounded_once(torch.log, self.alpha_t) - _rounded_once(torch.log, self.sigma_t)
-        self.init_noise_sigma = 1.0
-        self._acp_dev = {}
+        self._init_solver_tables(num_train_timesteps, beta_start, beta_end, beta_schedule)
         self.num_inference_steps = None
         self._set_list(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
         self.use_karras_sigmas = use_karras_sigmas
@@ -485,6 +490,194 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         return SchedulerOutput(prev_sample=prev)
 
 
+class UniPCMultistepScheduler(_SchedulerBase):
+    """scheduling_unipc_multistep.py:60-641, the UniPC predictor-corrector of orders 1 .. 3 (B(h) forms bh1 / bh2) for epsilon
+    models.  The corrector of a step reuses the model evaluation the next predictor needs, so `step` runs, in the reference's order,
+    convert_model_output, the UniC update of the PREVIOUS step's order on the old history and `last_sample`, and the UniP update
+    of this step's order on the new history -- ONE launch of dp_unipc_step (ops.unipc_step).  The tables and every per-step scalar
+    are 0-d fp32 torch arithmetic on the CPU in the reference's operation order (:339-382, :443-497), with sqrt, log and expm1
+    correctly rounded (_rounded_once) and the 2 x 2 / 3 x 3 systems of rhos_p / rhos_c solved in fp64 from the fp32 R and b and
+    rounded once, for the same reason: every host forms the same bits.  The timesteps are kept as a host list beside the `timesteps`
+    tensor, so `step` reads nothing back from the device.  The history is a ring of `solver_order` device buffers that the steps
+    write in turn, and the corrected sample lives in a buffer of the scheduler's own: neither the caller's `sample` nor the
+    model's output buffer is written.
+    Not carried (NotImplementedError): dynamic thresholding, `solver_p`, `trained_betas`, `sample` / `v_prediction` models,
+    solver_order above 3, models that predict a variance."""
+    order = 1
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'solver_order',
+                    'prediction_type', 'thresholding', 'dynamic_thresholding_ratio', 'sample_max_value', 'predict_x0',
+                    'solver_type', 'lower_order_final', 'disable_corrector', 'solver_p')
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', trained_betas=None,
+                 solver_order=2, prediction_type='epsilon', thresholding=False, dynamic_thresholding_ratio=0.995,
+                 sample_max_value=1.0, predict_x0=True, solver_type='bh2', lower_order_final=True, disable_corrector=[],
+                 solver_p=None):
+        if trained_betas is not None:
+            raise NotImplementedError('trained_betas is not on the hot path')
+        if prediction_type != 'epsilon':
+            raise NotImplementedError('prediction_type %s: only epsilon prediction is on the hot path' % prediction_type)
+        if thresholding:
+            raise NotImplementedError('thresholding (dynamic thresholding) is not on the hot path')
+        if solver_p is not None:
+            raise NotImplementedError('solver_p (a foreign predictor) is not part of this path')
+        if solver_type in ('midpoint', 'heun', 'logrho'):             # :169-173: the rewrite of register_to_config
+            solver_type = 'bh1'
+        if solver_type not in ('bh1', 'bh2'):
+            raise NotImplementedError('solver_type %s is not implemented' % solver_type)
+        if int(solver_order) < 1:
+            raise ValueError('solver_order must be at least 1')
+        if int(solver_order) > 3:
+            raise NotImplementedError('solver_order %d: the kernel carries orders 1 to 3' % solver_order)
+        self.config = SimpleNamespace(
+            num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+            trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
+            dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value, predict_x0=predict_x0,
+            solver_type=solver_type, lower_order_final=lower_order_final, disable_corrector=list(disable_corrector),
+            solver_p=solver_p)
+        self._init_solver_tables(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self.predict_x0 = predict_x0
+        self.num_inference_steps = None
+        self.disable_corrector = list(disable_corrector)
+        self.solver_p = None
+        self.timestep_list = [None] * solver_order
+        self.this_order = None
+        self._xc = None                                               # the corrected sample's buffer (last_sample after a corrector)
+        self._set_list(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
+
+    @classmethod
+    def from_config(cls, config):
+        d = vars(config) if not isinstance(config, dict) else config
+        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+    def scale_model_input(self, sample, *args, **kwargs):
+        return sample
+
+    def _set_list(self, ts, device=None):
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._ts = [int(v) for v in ts]                               # the host's copy: what `step` looks timesteps up in
+        self._index = {}
+        for i, v in enumerate(self._ts):
+            self._index.setdefault(v, i)
+        self.model_outputs = [None] * self.config.solver_order        # newest last, as the reference keeps them
+        self.lower_order_nums = 0
+        self.last_sample = None
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """:187-219: the rounded linspace, duplicates removed in order of appearance, the history reset (timestep_list is kept,
+        as the reference keeps it)."""
+        ts = (np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps + 1)
+              .round()[::-1][:-1].copy().astype(np.int64))
+        _, unique_indices = np.unique(ts, return_index=True)
+        ts = ts[np.sort(unique_indices)]
+        self._set_list(ts, device)
+        self.num_inference_steps = len(ts)
+
+    def update_coefs(self, order, s0, t, sis, corrector):
+        """The fp32 scalars of one UniP (:339-407) or UniC (:443-514) update of `order` from s0 to t, formed as the reference forms
+        them: (cx, c0, cB, rks, rhos) with x' = (cx x - c0 m0) - cB (sum_i rhos[i] D_i), D_i = (m_i - m0) / rks[i].  `sis`: the
+        order - 1 timesteps before s0, newest first.  The corrector's rhos carry one entry more, the factor of (m_t - m0)."""
+        lambda_t, lambda_s0 = self.lambda_t[t], self.lambda_t[s0]
+        alpha_t, alpha_s0 = self.alpha_t[t], self.alpha_t[s0]
+        sigma_t, sigma_s0 = self.sigma_t[t], self.sigma_t[s0]
+        h = lambda_t - lambda_s0
+        rks = [(self.lambda_t[si] - lambda_s0) / h for si in sis]
+        assert len(rks) == order - 1
+        rk_all = torch.tensor(rks + [1.0])
+        hh = -h if self.predict_x0 else h
+        h_phi_1 = _rounded_once(torch.expm1, hh)
+        h_phi_k = h_phi_1 / hh - 1
+        factorial_i = 1
+        B_h = hh if self.config.solver_type == 'bh1' else _rounded_once(torch.expm1, hh)
+        R, b = [], []
+        for i in range(1, order + 1):
+            R.append(torch.pow(rk_all, i - 1))
+            b.append(h_phi_k * factorial_i / B_h)
+            factorial_i *= i + 1
+            h_phi_k = h_phi_k / hh - 1 / factorial_i
+        R = torch.stack(R)
+        b = torch.tensor(b)
+
+        def solve(A, y):                                              # fp64 from the fp32 system, rounded once
+            return torch.linalg.solve(A.double(), y.double()).float()
+        if corrector:
+            rhos = torch.tensor([0.5]) if order == 1 else solve(R, b)
+        elif order == 1:
+            rhos = torch.zeros(0)
+        elif order == 2:
+            rhos = torch.tensor([0.5])
+        else:
+            rhos = solve(R[:-1, :-1], b[:-1])
+        if self.predict_x0:
+            cx, c0, cB = sigma_t / sigma_s0, alpha_t * h_phi_1, alpha_t * B_h
+        else:
+            cx, c0, cB = alpha_t / alpha_s0, sigma_t * h_phi_1, sigma_t * B_h
+        return float(cx), float(c0), float(cB), [float(v) for v in rks], [float(v) for v in rhos]
+
+    def step_coefs(self, pc, pp, timestep, prev_timestep, old_list):
+        """The scalars of one launch as ops.unipc_step names them.  `old_list`: timestep_list before this step, newest last."""
+        c = dict(sigma_s=float(self.sigma_t[timestep]), alpha_s=float(self.alpha_t[timestep]))
+        if pc:
+            sis = [old_list[-(i + 1)] for i in range(1, pc)]
+            cx, c0, cB, rks, rhos = self.update_coefs(pc, old_list[-1], timestep, sis, True)
+            c.update(c_cx=cx, c_c0=c0, c_cB=cB, c_rho_last=rhos[-1])
+            c.update({'c_rk%d' % (i + 1): v for i, v in enumerate(rks)})
+            c.update({'c_rho%d' % (i + 1): v for i, v in enumerate(rhos[:-1])})
+        new_list = list(old_list[1:]) + [timestep]
+        sis = [new_list[-(i + 1)] for i in range(1, pp)]
+        cx, c0, cB, rks, rhos = self.update_coefs(pp, timestep, prev_timestep, sis, False)
+        c.update(p_cx=cx, p_c0=c0, p_cB=cB)
+        c.update({'p_rk%d' % (i + 1): v for i, v in enumerate(rks)})
+        c.update({'p_rho%d' % (i + 1): v for i, v in enumerate(rhos)})
+        return c
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        """:518-600.  The corrector's order is the previous step's `this_order`, the predictor's the reference's choice
+        (solver_order, the steps that remain under lower_order_final, the lower_order_nums warm-up); exactly one launch, nothing
+        read back."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if model_output.shape[1] != sample.shape[1]:
+            raise NotImplementedError('a model output of %d channels for a sample of %d (a predicted variance) is not part of this path'
+                                      % (model_output.shape[1], sample.shape[1]))
+        ts = self._ts
+        last = len(ts) - 1
+        t = int(timestep)
+        i = self._index.get(t, last)
+        use_corrector = i > 0 and i - 1 not in self.disable_corrector and self.last_sample is not None
+        pc = self.this_order if use_corrector else 0
+        prev_t = 0 if i == last else ts[i + 1]
+        so = self.config.solver_order
+        this_order = min(so, len(ts) - i) if self.config.lower_order_final else so
+        pp = min(this_order, self.lower_order_nums + 1)
+        assert pp > 0
+        coef = self.step_coefs(pc, pp, t, prev_t, self.timestep_list)
+        sample = sample.contiguous()
+        hist = self.model_outputs
+        buf = hist[0]                                                 # the oldest buffer of the ring takes this step's output
+        if buf is None or buf.shape != sample.shape or buf.device != sample.device or any(buf is h for h in hist[1:]):
+            buf = torch.empty_like(sample)
+        xc = None
+        if pc:
+            xc = self._xc
+            if xc is None or xc.shape != sample.shape or xc.device != sample.device:
+                xc = self._xc = torch.empty_like(sample)
+        prev, xc, m_new = ops.unipc_step(model_output.contiguous(), sample, coef, pc=pc, pp=pp, predict_x0=self.predict_x0,
+                                         x_last=self.last_sample if pc else None, hist=hist[::-1][:max(pc, pp - 1)],
+                                         m_new=buf, x_c=xc)
+        self.model_outputs = hist[1:] + [m_new]
+        self.timestep_list = list(self.timestep_list[1:]) + [t]
+        self.this_order = pp
+        self.last_sample = xc if pc else sample
+        if self.lower_order_nums < so:
+            self.lower_order_nums += 1
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
 @dataclass
 class ImagePipelineOutput:
     images: object
@@ -571,11 +764,15 @@ class DDPMPipeline(_PipelineBase):
         image = randn_tensor(shape, generator=generator, device=self.device)
         self.scheduler.set_timesteps(num_inference_steps)
         ts = [int(t) for t in self.scheduler.timesteps.tolist()]              # one read-back instead of one per step
+        import inspect                                      # a deterministic scheduler's step (UniPC) takes no generator
+        params = inspect.signature(self.scheduler.step).parameters
+        takes = 'generator' in params or any(p.kind is p.VAR_KEYWORD for p in params.values())
+        extra = {'generator': generator} if takes else {}
         fwd = _sampling_forward(self.unet, shape, len(ts))  # weights pinned; the forward replayed natively where it pays
         try:
             for t in self.progress_bar(ts):
                 model_output = fwd(image, t)
-                image = self.scheduler.step(model_output, t, image, generator=generator).prev_sample
+                image = self.scheduler.step(model_output, t, image, **extra).prev_sample
         finally:
             fwd.close()
         return _to_output(self, image, output_type, return_dict)

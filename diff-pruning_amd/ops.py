@@ -2042,6 +2042,57 @@ def dpm_solver_step(x, e, coef, order=1, data_pred=True, m1=None, m2=None, out=N
     return out, m0_out
 
 
+UNIPC_MAX_BLOCKS = 4096              # DP_UNIPC_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
+UNIPC_COEF = ('sigma_s', 'alpha_s', 'c_cx', 'c_c0', 'c_cB', 'c_rk1', 'c_rk2', 'c_rho1', 'c_rho2', 'c_rho_last',
+              'p_cx', 'p_c0', 'p_cB', 'p_rk1', 'p_rk2', 'p_rho1', 'p_rho2')
+
+
+def unipc_step(e, x_pred, coef, pc=0, pp=1, predict_x0=True, x_last=None, hist=(), m_new=None, x_c=None, out=None):
+    """One step of the UniPC multistep scheduler (dp_unipc_step, csrc/unipc.hip) over flat fp32 data.  `coef`: the host's fp32 scalars
+    by name (UNIPC_COEF; one an instantiation does not read may be left out):
+    m_new = (x_pred - sigma_s e) / alpha_s (predict_x0) | e;
+    corrector `pc` in 0 (absent) .. 3 on the OLD history hist = (m0 newest, m1, m2) and x_last: D_i = (m_i - m0) / c_rk<i>,
+    x_c = (c_cx x_last - c_c0 m0) - c_cB ([c_rho1 D_1 [+ c_rho2 D_2]] + c_rho_last (m_new - m0));
+    predictor `pp` in 1 .. 3 on (m_new, m0, m1) from xs = x_c (pc > 0) | x_pred: E_1 = (m0 - m_new) / p_rk1, E_2 = (m1 - m_new) / p_rk2,
+    x' = (p_cx xs - p_c0 m_new) [- p_cB (p_rho1 E_1 [+ p_rho2 E_2])].
+    `hist`: at least max(pc, pp - 1) buffers, newest first; more are ignored.  `m_new` may be one of the history buffers read (the oldest
+    of the caller's ring), `x_c` may be `x_last`, `out` may be `x_pred`; no other buffer may be shared.  Returns (out, x_c, m_new), x_c
+    None when pc == 0."""
+    n = x_pred.numel()
+    assert pc in (0, 1, 2, 3) and pp in (1, 2, 3)
+    assert e.dtype == _f32 and x_pred.dtype == _f32 and e.is_contiguous() and x_pred.is_contiguous() and e.numel() == n
+    nh = max(pc, pp - 1)
+    hist = list(hist)[:nh]
+    assert len(hist) == nh and all(h is not None and h.dtype == _f32 and h.is_contiguous() and h.numel() == n for h in hist), \
+        'unipc_step: history below the orders'
+    if pc:
+        assert x_last is not None and x_last.dtype == _f32 and x_last.is_contiguous() and x_last.numel() == n, 'unipc_step: corrector without x_last'
+        if x_c is None:
+            x_c = torch.empty_like(x_pred)
+    else:
+        x_last = x_c = None
+    if out is None:
+        out = torch.empty_like(x_pred)
+    if m_new is None:
+        m_new = torch.empty_like(x_pred)
+    outs = [o for o in (m_new, x_c, out) if o is not None]
+    for o in outs:
+        assert o.dtype == _f32 and o.is_contiguous() and o.numel() == n
+    assert len({o.data_ptr() for o in outs}) == len(outs)
+    hp = [h.data_ptr() for h in hist]
+    lp = [x_last.data_ptr()] if pc else []
+    assert m_new.data_ptr() not in [e.data_ptr(), x_pred.data_ptr()] + lp
+    assert out.data_ptr() not in [e.data_ptr()] + lp + hp
+    assert x_c is None or x_c.data_ptr() not in [e.data_ptr(), x_pred.data_ptr()] + hp
+    unknown = set(coef) - set(UNIPC_COEF)
+    assert not unknown, unknown
+    c = L.UniPCCoef(**{k: float(v) for k, v in coef.items()})
+    h = [_p(t) for t in hist] + [None] * (3 - nh)
+    L.check(_lib().dp_unipc_step(_p(e), _p(x_pred), _p(x_last) if pc else None, h[0], h[1], h[2], int(pc), int(pp), 1 if predict_x0 else 0,
+                                 C.byref(c), _p(m_new), _p(x_c) if pc else None, _p(out), n, _stream()), 'dp_unipc_step')
+    return out, x_c, m_new
+
+
 # --------------------------------------------------------------------------------------------------
 # LDM transformer-block glue (channel-major tokens [N, C, H, W] == [N][C][T])
 # --------------------------------------------------------------------------------------------------

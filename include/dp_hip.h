@@ -572,6 +572,38 @@ typedef struct dp_dpm_solver_coef {
 int dp_dpm_solver_step(const float* x, const float* e, const float* m1, const float* m2, int order, int data_pred,
                        const dp_dpm_solver_coef* coef, float* x_next, float* m0_out, long long n, void* stream);
 
+/* One step of the UniPC multistep scheduler (csrc/unipc.hip; diffusers/schedulers/scheduling_unipc_multistep.py:256-305 epsilon
+ * prediction, :307-410 UniP, :412-516 UniC, chained as :518-600 chains them) over n fp32 elements, one pass:
+ *   m_new = predict_x0 ? (x_pred - sigma_s * e) / alpha_s : e                       x_pred: the sample handed to `step`, uncorrected
+ *   corrector, pc in 0 (absent) .. 3, on the OLD history m0 (newest), m1, m2 and on x_last (the sample before the last predictor):
+ *     D_i = (m_i - m0) / c_rk<i>, i = 1 .. pc - 1;   dt = m_new - m0
+ *     x_c = (c_cx * x_last - c_c0 * m0) - c_cB * ([c_rho1 * D_1 [+ c_rho2 * D_2]] + c_rho_last * dt)
+ *   predictor, pp in 1 .. 3, on the NEW history (m_new, m0, m1), from xs = pc ? x_c : x_pred:
+ *     E_1 = (m0 - m_new) / p_rk1;  E_2 = (m1 - m_new) / p_rk2
+ *     x_next = (p_cx * xs - p_c0 * m_new) [- p_cB * (p_rho1 * E_1 [+ p_rho2 * E_2])]       (pp 2: the host passes p_rho1 = 0.5)
+ * every operation rounded separately, true divisions; the two history products of a third-order sum are added first, left to right,
+ * then (corrector) c_rho_last * dt is added to their sum.  The scalars are the host's 0-d fp32 arithmetic on the alpha_t / sigma_t /
+ * lambda_t tables.  Fields an instantiation does not read are ignored.
+ * Reads: e, x_pred, x_last (pc > 0), and the first max(pc, pp - 1) of m0, m1, m2; the others may be NULL.  Writes: m_new (always; a
+ * copy of e without predict_x0: the history owns its buffers), x_c (pc > 0: the next step's last_sample; may be NULL at pc 0), x_next.
+ * Aliases: `m_new` may be `m0`, `m1` or `m2` itself (the oldest buffer of a ring of solver_order history buffers, which this very
+ * step may still read), `x_c` may be `x_last` itself, `x_next` may be `x_pred` itself: each lane reads every input of its elements
+ * before it writes any of them, and no other lane touches them.  Any other overlap between an output and another buffer is
+ * hipErrorInvalidValue, as are a null required pointer, pc outside 0 .. 3 and pp outside 1 .. 3: nothing is launched.  n <= 0 is a no-op.
+ * 16-byte accesses between a scalar head and tail when all pointers in use share one alignment modulo 16, 4-byte accesses
+ * otherwise; any n (long long indexing, grid-stride beyond DP_UNIPC_MAX_BLOCKS blocks of 256 lanes). */
+#define DP_UNIPC_MAX_BLOCKS 4096
+typedef struct dp_unipc_coef {
+    float sigma_s, alpha_s;             /* convert (predict_x0 only) */
+    float c_cx, c_c0, c_cB;             /* corrector: the first-order part and the factor of the sum */
+    float c_rk1, c_rk2, c_rho1, c_rho2, c_rho_last;
+    float p_cx, p_c0, p_cB;             /* predictor */
+    float p_rk1, p_rk2, p_rho1, p_rho2;
+} dp_unipc_coef;
+int dp_unipc_step(const float* e, const float* x_pred, const float* x_last, const float* m0, const float* m1, const float* m2,
+                  int pc, int pp, int predict_x0, const dp_unipc_coef* coef, float* m_new, float* x_c, float* x_next, long long n,
+                  void* stream);
+
 /* ---- LDM (CompVis) transformer-block glue on channel-major tokens x[n][c][t]  (ldm_exp/ldm/modules/attention.py) ---- */
 /* LayerNorm over the C channels of every token (attention.py:200-212 norm1/2/3); stats[(n*T+t)*2+{0,1}] = {mean, rstd}. */
 int dp_layernorm_fwd(const float* x, long long x_img_stride, const float* gamma, const float* beta, int N, int C, int T,
