@@ -616,6 +616,14 @@ __global__ __launch_bounds__(256, (BM == 64 && BN == 128) ? 2 : 4) void conv_gem
 #ifndef DP_FAST_MINBLOCKS
 #define DP_FAST_MINBLOCKS 4
 #endif
+// The two fast kernels move their gathered-operand descriptor bases back by the padding and by the largest 12-bit instruction
+// offset they use: num_records grows by the same bytes, and the host rules (conv_fast_ok / nt_fast_ok) keep it below the
+// out-of-range marker DP_OOB (a marker inside the descriptor would load the tensor's tail instead of 0.0f).
+constexpr unsigned CONV_FAST_IMM_MAX = 3 * 1024;
+constexpr unsigned NT_FAST_IMM_MAX = 7 * (4 * 16 + 1) * 4;
+static bool dp_shifted_reach_ok(unsigned bytes, long long shift_bytes) {
+    return (long long)bytes + shift_bytes < (long long)DP_OOB;
+}
 // TAILS = false: every chunk is 16 channels wide (C % 16 == 0, split % 16 == 0): the K-tile bookkeeping is one scalar compare.
 // X4 (output rows a multiple of 4 pixels wide, at most one padding column per side): the B tile is fetched with TWO
 //   16-byte LDS-DMA loads per lane instead of eight 4-byte ones -- a lane owns 4 consecutive pixels of one channel row,
@@ -673,7 +681,7 @@ __global__ __launch_bounds__(256, DP_FAST_MINBLOCKS) void conv_gemm_fast_kernel(
     // descriptor bases moved back by the padding (never-negative scalar offsets) and by IMM_MAX bytes: the 8 B-tile
     // loads of a lane land 1 KB apart in LDS, so 4 of them share one M0 and differ in the 12-bit instruction offset --
     // which the hardware adds to the memory address too; the per-lane offsets carry the compensation (IMM_MAX - imm).
-    constexpr unsigned IMM_MAX = 3 * 1024;
+    constexpr unsigned IMM_MAX = CONV_FAST_IMM_MAX;
     const int shift = g.pad_t * g.Ws + g.pad_l + (int)(IMM_MAX / 4);
     const __amdgpu_buffer_rsrc_t rA = dp_rsrc(Ab, p.a_bytes);
     const __amdgpu_buffer_rsrc_t r1 = dp_rsrc(X1 - shift, p.x1_bytes + 4u * (unsigned)shift);
@@ -936,8 +944,11 @@ __global__ __launch_bounds__(256, DP_FAST_MINBLOCKS) void conv_gemm_fast_kernel(
 static bool conv_fast_ok(const dp_conv_gemm_params& p) {
     static const bool no_fast = getenv("DP_NO_FAST") != nullptr;
     const dp_conv_geom& g = p.g;
-    return !no_fast && !p.a_kc && g.stride == 1 && g.sden == 1 && g.ups == 0 && p.ntaps <= 32 && g.Hs == g.Hv &&
-           g.Ws == g.Wv;
+    if (no_fast || p.a_kc || g.stride != 1 || g.sden != 1 || g.ups != 0 || p.ntaps > 32 || g.Hs != g.Hv || g.Ws != g.Wv) return false;
+    // the X descriptors start `shift` floats in front of the tensor (num_records = extent + 4 shift): the out-of-range marker
+    // 0x80000000 must stay outside them, else a padded tap loads the tensor's tail.  conv_gemm_kernel's descriptors are unshifted.
+    const long long shift_bytes = 4ll * ((long long)g.pad_t * g.Ws + g.pad_l) + CONV_FAST_IMM_MAX;
+    return dp_shifted_reach_ok(p.x1_bytes, shift_bytes) && (!p.X2 || dp_shifted_reach_ok(p.x2_bytes, shift_bytes));
 }
 
 static bool conv_fast_tails(const dp_conv_gemm_params& p) {
@@ -1436,7 +1447,8 @@ __global__ __launch_bounds__(NW * 64, 4) void nt_gemm_fast_kernel(const dp_nt_ge
     // The 8 DMA groups of a lane are GRP dwords apart in LDS: one M0 per operand, the 12-bit instruction offset picks
     // the group.  The hardware adds that offset to the memory address too: bases are moved back by IMM_MAX bytes and the
     // per-lane offsets carry (IMM_MAX - imm).
-    constexpr unsigned IMM_MAX = 7 * GRP * 4;
+    constexpr unsigned IMM_MAX = NT_FAST_IMM_MAX;
+    static_assert(IMM_MAX == 7 * GRP * 4, "the last of the 8 DMA groups of a lane");
     const int shift = g.pad_t * g.Ws + g.pad_l + (int)(IMM_MAX / 4);
     const __amdgpu_buffer_rsrc_t rA = dp_rsrc(p.A - IMM_MAX / 4, p.a_bytes + IMM_MAX);
     const __amdgpu_buffer_rsrc_t rB1 = dp_rsrc(p.X1 - shift, p.x1_bytes + 4u * (unsigned)shift);
@@ -1595,9 +1607,15 @@ static bool nt_fast_ok(const dp_nt_gemm_params& p) {
     static const bool no_fast = getenv("DP_NO_FAST") != nullptr;
     const dp_conv_geom& g = p.g;
     const int HoWo = g.Ho * g.Wo;
-    return !no_fast && !p.batched && !p.merge && !p.col_bias && g.stride == 1 && g.sden == 1 && g.ups == 0 && g.Wo > 0 &&
-           ((g.Wo % 16) == 0 || (16 % g.Wo) == 0) && (HoWo % 16) == 0 && (p.P % 16) == 0 && (p.p_per_split % 16) == 0 &&
-           g.Hs == g.Hv && g.Ws == g.Wv;
+    if (!(!no_fast && !p.batched && !p.merge && !p.col_bias && g.stride == 1 && g.sden == 1 && g.ups == 0 && g.Wo > 0 &&
+          ((g.Wo % 16) == 0 || (16 % g.Wo) == 0) && (HoWo % 16) == 0 && (p.P % 16) == 0 && (p.p_per_split % 16) == 0 &&
+          g.Hs == g.Hv && g.Ws == g.Wv))
+        return false;
+    // same rule as conv_fast_ok: all three descriptors are longer than their tensors (A by the instruction offsets, X also by the
+    // padding) and must not reach the 0x80000000 marker.  nt_gemm_kernel's descriptors are unshifted.
+    const long long shift_bytes = 4ll * ((long long)g.pad_t * g.Ws + g.pad_l) + NT_FAST_IMM_MAX;
+    return dp_shifted_reach_ok(p.a_bytes, NT_FAST_IMM_MAX) && dp_shifted_reach_ok(p.x1_bytes, shift_bytes) &&
+           (!p.X2 || dp_shifted_reach_ok(p.x2_bytes, shift_bytes));
 }
 
 template <int BM, int BN>

@@ -67,11 +67,23 @@ def _run(call, name, flops, abytes=0.0):
     return r
 
 
+_CONV_FAST_IMM_MAX = 3 * 1024               # CONV_FAST_IMM_MAX / NT_FAST_IMM_MAX of csrc/gemm.hip: bytes the fast kernels move
+_NT_FAST_IMM_MAX = 7 * (4 * 16 + 1) * 4     # their descriptor bases back by, on top of the padding
+
+
+def _shifted_reach_ok(p, imm_max):
+    """The gathered-operand descriptors of the fast kernels start pad_t rows + pad_l columns + imm_max bytes in front of the tensor and
+    are that much longer: refused when one of them would reach the out-of-range marker, bit 31 of a byte offset (dp_shifted_reach_ok in
+    csrc/gemm.hip)."""
+    shift_bytes = 4 * (p.g.pad_t * p.g.Ws + p.g.pad_l) + imm_max
+    return p.x1_bytes + shift_bytes < _MAX_BYTES and (not p.X2 or p.x2_bytes + shift_bytes < _MAX_BYTES)
+
+
 def _conv_fast_ok(p):
     """Same rule as conv_fast_ok() in csrc/gemm.hip: the stride-1 / no-upsample loader applies."""
     g = p.g
     return (not p.a_kc and g.stride == 1 and g.sden == 1 and g.ups == 0 and p.ntaps <= 32 and g.Hs == g.Hv
-            and g.Ws == g.Wv and not os.environ.get('DP_NO_FAST'))
+            and g.Ws == g.Wv and not os.environ.get('DP_NO_FAST') and _shifted_reach_ok(p, _CONV_FAST_IMM_MAX))
 
 
 def _prefer_tile96(p):
@@ -115,17 +127,20 @@ def _cg_name(p):
                                              'true' if straddle else 'false')
 
 
-def _nt_fast_geom_ok(g, P, batched=False, merge=False, col_bias=False):
-    """Same rule as nt_fast_ok() in csrc/gemm.hip (p_per_split is always a multiple of 32 here)."""
-    return (not batched and not merge and not col_bias and g.stride == 1 and g.sden == 1 and g.ups == 0 and g.Wo > 0
-            and (g.Wo % 16 == 0 or 16 % g.Wo == 0) and (g.Ho * g.Wo) % 16 == 0 and P % 16 == 0
-            and g.Hs == g.Hv and g.Ws == g.Wv and not os.environ.get('DP_NO_FAST'))
+def _nt_fast_ok(p):
+    """Same rule as nt_fast_ok() in csrc/gemm.hip, term by term: the geometry, then the extents -- the A descriptor is longer than its
+    tensor by the instruction offsets, the X descriptors also by the padding, and none may reach the out-of-range marker."""
+    g = p.g
+    return (not p.batched and not p.merge and not p.col_bias and g.stride == 1 and g.sden == 1 and g.ups == 0 and g.Wo > 0
+            and (g.Wo % 16 == 0 or 16 % g.Wo == 0) and (g.Ho * g.Wo) % 16 == 0 and p.P % 16 == 0 and p.p_per_split % 16 == 0
+            and g.Hs == g.Hv and g.Ws == g.Wv and not os.environ.get('DP_NO_FAST')
+            and p.a_bytes + _NT_FAST_IMM_MAX < _MAX_BYTES and _shifted_reach_ok(p, _NT_FAST_IMM_MAX))
 
 
 def _nt_name(p):
     if p.merge:
         return 'nt_gemm_kernel<64, 64, false, true>'
-    if p.tile in (0, 3) and _nt_fast_geom_ok(p.g, p.P, p.batched, p.merge, bool(p.col_bias)) and p.p_per_split % 16 == 0:
+    if p.tile in (0, 3) and _nt_fast_ok(p):
         return 'nt_gemm_fast_kernel<%d, %s>' % (4 if p.tile == 0 else 3, 'true' if p.X2 else 'false')
     t = 0 if p.tile == 3 else p.tile
     straddle = bool(p.X2) and (p.g.c_split % _TILES[t][1]) != 0
@@ -150,7 +165,11 @@ def _extent_bytes(x):
         return 0
     N, Cc, H, W = x.shape
     s0 = x.stride(0) if N > 1 else 0
-    n = ((N - 1) * s0 + Cc * H * W) * 4
+    return _checked_bytes(((N - 1) * s0 + Cc * H * W) * 4)
+
+
+def _checked_bytes(n):
+    """n, the byte extent one descriptor covers (an activation view, or one matrix of a batched product), refused from 2 GiB on."""
     if n >= _MAX_BYTES:
         raise ValueError('tensor extent %d bytes >= 2 GiB (32-bit buffer addressing): run the shard in micro-batches, '
                          'e.g. taylor_sweep(..., micro_batch=16)' % n)
@@ -622,7 +641,7 @@ def _conv_gemm_params(A, lda, x, x2, geom, M, K, NPIX, ntaps, out, o_img_stride,
         p.a_bytes, p.x1_bytes, p.x2_bytes = A.numel() * 4, _extent_bytes(x), _extent_bytes(x2)
     else:
         p.x_guard = 1
-        p.a_bytes, p.x1_bytes, p.x2_bytes = M * K * 4, K * NPIX * 4, 0
+        p.a_bytes, p.x1_bytes, p.x2_bytes = _checked_bytes(M * K * 4), _checked_bytes(K * NPIX * 4), 0
     p.g = geom
     p.M, p.C, p.NPIX, p.ntaps, p.batches = M, K, NPIX, ntaps, Z
     p.tile = pick_tile(M, NPIX, Z)
@@ -997,7 +1016,7 @@ def _nt_gemm_params(A, a_img_stride, x, x2, geom, M, Cc, ncols, ntaps, P, splits
     if batch is None:
         p.a_bytes, p.x1_bytes, p.x2_bytes = _extent_bytes(A), _extent_bytes(x), _extent_bytes(x2)
     else:
-        p.a_bytes, p.x1_bytes, p.x2_bytes = M * P * 4, ncols * P * 4, 0
+        p.a_bytes, p.x1_bytes, p.x2_bytes = _checked_bytes(M * P * 4), _checked_bytes(ncols * P * 4), 0
     p.g = geom
     p.M, p.C, p.NCOLS, p.ntaps, p.P = M, Cc, ncols, ntaps, P
     p.batches, p.splits, p.p_per_split, p.tile, p.batched = Z, splits, pps, tile, batched
@@ -1116,7 +1135,10 @@ def conv_wgrad(dy, x, x2, gw, spec, *, alpha=1.0, accumulate=True, max_splits=No
                  C1 if x2 is not None else Cin, s1, s2)
     tile = 0 if Cout > 64 else 1
     bm, bn, _ = _TILES[tile]
-    if tile == 0 and _nt_fast_geom_ok(geom, P):
+    # the block first (extents checked, one slice of 32 pixels for now): the fast kernel's rule looks at the extents too, and the
+    # tile, the grid and the slices below are sized for the kernel that will run
+    p = _nt_gemm_params(dy, sd, x, x2, geom, Cout, Cin, Cin, taps, P, 1, 32, tile, alpha, ncols)
+    if tile == 0 and _nt_fast_ok(p):
         # pruned widths (90, 180, ...): 96x96 tiles when they cover [Cout x Cin] with clearly less padding
         a96 = (-(-Cout // 96) * 96) * (-(-Cin // 96) * 96)
         a128 = (-(-Cout // 128) * 128) * (-(-Cin // 128) * 128)
@@ -1132,7 +1154,7 @@ def conv_wgrad(dy, x, x2, gw, spec, *, alpha=1.0, accumulate=True, max_splits=No
     pps = -(-P // splits)
     pps = (pps + 31) & ~31
     splits = -(-P // pps)
-    p = _nt_gemm_params(dy, sd, x, x2, geom, Cout, Cin, Cin, taps, P, splits, pps, tile, alpha, ncols)
+    p.splits, p.p_per_split, p.tile = splits, pps, tile
     p.xcd = 0 if os.environ.get('DP_NO_XCD') else 1
     return _wgrad_launch(p, gw, accumulate, 'dp_nt_gemm', _nt_name(p), 2.0 * p.M * p.NCOLS * p.ntaps * p.P, 'dp_nt_gemm(wgrad)', taps,
                          dy.device)

@@ -2361,6 +2361,84 @@ def test_winograd_refuses_activations_within_a_row_of_2gib():
     assert wgrad(4 << 20) == 1 and wgrad(lim - 4) == 1 and wgrad(lim) == 0
 
 
+def test_fast_kernels_refuse_activations_within_their_shift_of_2gib():
+    """The same hazard in csrc/gemm.hip: conv_gemm_fast_kernel and nt_gemm_fast_kernel move their gathered-operand descriptor bases back
+    by `shift` = pad_t * Ws + pad_l floats + the largest instruction offset (3072 / 1820 bytes), the nt form its A base by 1820 bytes,
+    and lengthen num_records by as much.  conv_fast_ok / nt_fast_ok refuse whenever a descriptor would reach 0x80000000; they are not
+    exported, so what is pinned here is their ops mirrors (_conv_fast_ok, _nt_fast_ok) -- the names ops gives the profiler, which tests/test_reach_gpu.py holds
+    equal to the launched kernels on both sides of the rule -- and the ValueError of the batched parameter blocks."""
+    ops, L = pkg('ops'), pkg('_lib')
+    assert ops._CONV_FAST_IMM_MAX == 3 * 1024 and ops._NT_FAST_IMM_MAX == 7 * 65 * 4 and ops._MAX_BYTES == 1 << 31
+
+    def conv(x1_bytes, x2_bytes=0, tile=0, W=16):
+        p = L.ConvGemmParams()
+        p.g = ops._geom(16, W, 16, W, 16, W, 3, 1, 1, 1, 1, 0, 64, 0, 0)
+        p.M, p.C, p.NPIX, p.ntaps, p.batches, p.a_kc, p.tile, p.x_guard = 100, 128 if x2_bytes else 64, 512, 9, 1, 0, tile, 1
+        p.x1_bytes, p.x2_bytes = x1_bytes, x2_bytes
+        if x2_bytes:
+            p.X2 = 16
+        return p
+
+    for W in (16, 18):
+        lim = (1 << 31) - 4 * (W + 1) - 3072                     # extent + 4 shift must stay below 0x80000000
+        x4 = 'true' if W % 4 == 0 else 'false'
+        assert ops._conv_fast_ok(conv(lim - 4, W=W)) and not ops._conv_fast_ok(conv(lim, W=W)) and not ops._conv_fast_ok(conv((1 << 31) - 4, W=W))
+        assert ops._conv_fast_ok(conv(1 << 20, lim - 4, W=W)) and not ops._conv_fast_ok(conv(1 << 20, lim, W=W))
+        assert ops._conv_fast_ok(conv(lim - 4, lim - 4, W=W)) and not ops._conv_fast_ok(conv(lim, 1 << 20, W=W))
+        assert ops._cg_name(conv(lim - 4, W=W)) == 'conv_gemm_fast_kernel<128, 128, false, %s>' % x4
+        assert ops._cg_name(conv(lim, W=W)) == 'conv_gemm_kernel<128, 128, false, false>'
+        assert ops._cg_name(conv(1 << 20, lim - 4, W=W)) == 'conv_gemm_fast_kernel<128, 128, false, %s>' % x4
+        assert ops._cg_name(conv(1 << 20, lim, W=W)) == 'conv_gemm_kernel<128, 128, false, false>'
+        assert ops._cg_name(conv(lim - 4, tile=3, W=W)) == 'conv_gemm_fast_kernel<96, 128, true, %s>' % x4
+        assert ops._cg_name(conv(lim, tile=3, W=W)) == 'conv_gemm_kernel<128, 128, false, false>'       # tile 3 / 4 without the fast loader: 128 x 128
+        p = conv(lim, W=W)
+        p.tile = 1
+        ops._prefer_tile96(p)
+        assert p.tile == 1                                       # no 128- / 96-row preference for a launch the fast kernels refuse
+    # the x2 extent only counts when there is a second source
+    p = conv(1 << 20)
+    p.x2_bytes = (1 << 31) - 4
+    assert ops._conv_fast_ok(p)
+
+    def nt(a_bytes, x1_bytes, x2_bytes=0, tile=0):
+        p = L.NtGemmParams()
+        p.g = ops._geom(16, 16, 16, 16, 16, 16, 3, 1, 1, 1, 1, 0, 64, 0, 0)
+        p.M, p.C, p.NCOLS, p.ntaps, p.P = 100, 64, 128 if x2_bytes else 64, 9, 512
+        p.batches, p.splits, p.p_per_split, p.tile = 1, 1, 512, tile
+        p.a_bytes, p.x1_bytes, p.x2_bytes = a_bytes, x1_bytes, x2_bytes
+        if x2_bytes:
+            p.X2 = 16
+        return p
+
+    lim_a = (1 << 31) - 1820                                     # A: num_records = extent + 1820
+    lim_x = (1 << 31) - 4 * 17 - 1820                            # X: extent + 4 (Ws + 1) + 1820
+    small = 1 << 20
+    # (conv_wgrad asks _nt_fast_ok before it prefers 96 x 96 tiles, so tile, grid and slices are sized for the kernel that runs)
+    assert ops._nt_fast_ok(nt(lim_a - 4, lim_x - 4, lim_x - 4)) and not ops._nt_fast_ok(nt(lim_a, small)) and not ops._nt_fast_ok(nt(small, lim_x))
+    assert not ops._nt_fast_ok(nt(small, small, lim_x)) and ops._nt_fast_ok(nt(small, small))
+    for tile, nw in ((0, 4), (3, 3)):
+        fast, slow = 'nt_gemm_fast_kernel<%d, %%s>' % nw, 'nt_gemm_kernel<128, 128, %s, false>'
+        assert ops._nt_name(nt(small, small, tile=tile)) == fast % 'false'
+        assert ops._nt_name(nt(lim_a - 4, small, tile=tile)) == fast % 'false' and ops._nt_name(nt(lim_a, small, tile=tile)) == slow % 'false'
+        assert ops._nt_name(nt(small, lim_x - 4, tile=tile)) == fast % 'false' and ops._nt_name(nt(small, lim_x, tile=tile)) == slow % 'false'
+        assert ops._nt_name(nt(small, small, lim_x - 4, tile=tile)) == fast % 'true'
+        assert ops._nt_name(nt(small, small, lim_x, tile=tile)) == slow % 'true'             # c_split = 64: an N tile of 128 spans both sources
+        assert ops._nt_name(nt(small, small, (1 << 31) - 4, tile=tile)) == slow % 'true'
+
+    # batched products take their operand extents from the matrix shapes: 2 GiB per matrix is refused like a 2 GiB activation view
+    t = torch.empty(4)
+    for M, K, Nn in ((1 << 15, 1 << 14, 4), (4, 1 << 14, 1 << 15), (1 << 16, 1 << 16, 4)):     # A = 2^31, X = 2^31, A = 2^34 (wraps a c_uint)
+        with pytest.raises(ValueError, match='2 GiB'):
+            ops._conv_gemm_params(t, M, t, None, ops._bgeom(Nn, K), M, K, Nn, 1, t, 0, batch=(2, M * K, K * Nn, M * Nn))
+        with pytest.raises(ValueError, match='2 GiB'):
+            ops._nt_gemm_params(t, 0, t, None, ops._bgeom(K, Nn), M, Nn, Nn, 1, K, 1, 0, 0, 1.0, Nn, batch=(2, M * K, K * Nn, 1))
+    M, K, Nn = (1 << 15) - 1, 1 << 14, 4                         # one row fewer: accepted, extents as the matrix shapes say
+    p = ops._conv_gemm_params(t, M, t, None, ops._bgeom(Nn, K), M, K, Nn, 1, t, 0, batch=(2, M * K, K * Nn, M * Nn))
+    assert (p.a_bytes, p.x1_bytes, p.x2_bytes) == (M * K * 4, K * Nn * 4, 0) and p.a_bytes == (1 << 31) - (1 << 16)
+    p = ops._nt_gemm_params(t, 0, t, None, ops._bgeom(K, Nn), M, Nn, Nn, 1, K, 1, 0, 0, 1.0, Nn, batch=(2, M * K, K * Nn, 1))
+    assert (p.a_bytes, p.x1_bytes, p.x2_bytes) == (M * K * 4, Nn * K * 4, 0)
+
+
 def test_lsun_ffhq_lmdb_datasets(tmp_path):
     """SURVEY §8(f) rank 4, the LSUN / FFHQ half (ddpm_exp/datasets/lsun.py:11-173, ffhq.py:8-40, __init__.py:109-157): LMDB
     environments read by the package's own pure-Python reader (lmdb_reader.py; `lmdb` is not in this image).  The environments are
