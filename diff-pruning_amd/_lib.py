@@ -98,6 +98,12 @@ class Ups9FwdParams(C.Structure):
                 ('u_bytes', C.c_uint), ('x_bytes', C.c_uint)] + [(n, C.c_int) for n in ('ldu', 'N', 'M', 'K', 'H', 'W')]
 
 
+class Ups9WgradParams(C.Structure):
+    _fields_ = [('dy', C.c_void_p), ('x', C.c_void_p), ('ws', C.c_void_p), ('gw', C.c_void_p), ('dy_img_stride', LL), ('x_img_stride', LL),
+                ('ws_floats', LL), ('dy_bytes', C.c_uint), ('x_bytes', C.c_uint)] + [(n, C.c_int) for n in (
+                    'N', 'Co', 'Ci', 'H', 'W', 'splits', 'tiles_per_split', 'ld', 'accumulate')]
+
+
 class ColsumItem(C.Structure):
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('N', C.c_int), ('C', C.c_int), ('wstride', C.c_int),
                 ('woff', C.c_int), ('accumulate', C.c_int), ('ld', C.c_int)]
@@ -176,6 +182,8 @@ SIGNATURES = {
     'dp_ups9_dgrad': [C.POINTER(Ups9Params), _vp],
     'dp_ups9_dgrad_supported': [C.POINTER(Ups9Params)],
     'dp_ups9_fwd': [C.POINTER(Ups9FwdParams), _vp],
+    'dp_ups9_wgrad': [C.POINTER(Ups9WgradParams), _vp],
+    'dp_ups9_wgrad_reduce': [C.POINTER(Ups9WgradParams), _vp],
     'dp_wg_reduce': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp],
     'dp_gather_add': [_vp, _vp, _i, _vp, _vp],
     'dp_group_score': [C.POINTER(ScoreMember), _i, _i, _vp, _vp, _vp, _vp],

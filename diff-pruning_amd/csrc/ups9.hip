@@ -6,8 +6,8 @@
 // y[2i] = m0 + m1, y[2i+1] = m1 + m2.  In two dimensions U = G w G^T (3x3 per (co, ci), integer combinations, dp_ups9_u) with
 // G = [1 0 0; 1 1 1; 0 0 1], and nine products per pixel.
 //
-// This file holds the INPUT GRADIENT and the FORWARD pass of that form (ups9_fwd_kernel, further down); the weight gradient keeps the class
-// launches.  The input gradient:
+// This file holds the INPUT GRADIENT and the FORWARD pass of that form (ups9_fwd_kernel, further down); the weight gradient is
+// csrc/ups9_wgrad.hip.  The input gradient:
 //     dx[n][ci][i][j] = sum_co sum_{a,b} U[co][ci][a][b] T[n][co][a][b][i][j],   T = R p R^T,
 // p = the 4x4 patch of the HIGH-resolution dy at rows 2i-1 .. 2i+2 / columns 2j-1 .. 2j+2 (zero outside the image) and
 // R = [0 -1 0 1; 0 1 1 0; 1 0 -1 0] (T0 = p3 - p1, T1 = p1 + p2, T2 = p0 - p2 along each axis): one implicit GEMM with nine taps

@@ -544,7 +544,8 @@ class UNetEngine:
     # pixel and channel pair, in the forward pass, the input gradient and the weight gradient alike.  Where the measured gates take the
     # shape (ops.ups9_fwd_wanted / ops.ups9_dgrad_wanted), the forward pass and the input gradient run in NINE products per pixel
     # instead (U = G w G^T, csrc/ups9.hip): one launch each, reading x / dy and writing y / dx where they lie, so that the forward has
-    # no class staging buffer and no interleave pass.  The weight gradient keeps the class form.
+    # no class staging buffer and no interleave pass; and where ops.ups9_wgrad_wanted takes it the weight gradient is the launch pair of
+    # csrc/ups9_wgrad.hip (nine position GEMMs over the pixels + one reduce-and-fold launch): no de-interleaved dy, no class gradients.
     def _ups_conv_fwd(self, name, x):
         w = self.P[name + '.weight']
         N, _, H, W = x.shape
@@ -564,18 +565,24 @@ class UNetEngine:
         # the input gradient in nine products per pixel straight from the high-resolution dy (csrc/ups9.hip) where the gate takes the
         # shape: the class kernels below then serve the weight gradient alone, and their de-interleave pass moves to its stream
         use9 = hasattr(ops, 'ups9_dgrad_wanted') and ops.ups9_dgrad_wanted(x.shape[0], w.shape[1], w.shape[0], x.shape[2], x.shape[3])
+        # ... and the weight gradient likewise (csrc/ups9_wgrad.hip: one launch pair, no class gradients, no fold launch); with both on
+        # that path nothing reads a de-interleaved dy any more
+        wg9 = hasattr(ops, 'ups9_wgrad_wanted') and ops.ups9_wgrad_wanted(x.shape[0], w.shape[1], w.shape[0], x.shape[2], x.shape[3])
         dyq = None if use9 else ops.deinterleave2x2(dy)
         rows = None
         if (name + '.bias') in self.P and self._rows_src is not None and self._rows_src[0].data_ptr() == dy.data_ptr():
             rows = self._rows_of(dy)
 
         def param_grads(rows, dyq=dyq):
-            if dyq is None:
-                dyq = ops.deinterleave2x2(dy)
-            gweff = torch.empty((4,) + tuple(w.shape[:2]) + (2, 2), dtype=torch.float32, device=dy.device)
-            for c, spec in enumerate(_UPS_SPECS):
-                ops.conv_wgrad(dyq[c], x, None, gweff[c], spec, accumulate=False)
-            ops.ups_wfold(gweff, self.G[name + '.weight'], accumulate=True)
+            if wg9:
+                ops.ups9_wgrad(dy, x, self.G[name + '.weight'])
+            else:
+                if dyq is None:
+                    dyq = ops.deinterleave2x2(dy)
+                gweff = torch.empty((4,) + tuple(w.shape[:2]) + (2, 2), dtype=torch.float32, device=dy.device)
+                for c, spec in enumerate(_UPS_SPECS):
+                    ops.conv_wgrad(dyq[c], x, None, gweff[c], spec, accumulate=False)
+                ops.ups_wfold(gweff, self.G[name + '.weight'], accumulate=True)
             if (name + '.bias') in self.P:
                 if rows is None:
                     rows = ops.rowsum_nc(dy)

@@ -971,6 +971,107 @@ def ups9_fwd(x, up, ldu, Cout, *, bias=None, out=None):
     return out
 
 
+# ---- ... and the weight gradient (csrc/ups9_wgrad.hip): dp_ups9_wgrad + dp_ups9_wgrad_reduce instead of deinterleave2x2, four class
+# launches with their split-K reductions, and ups_wfold
+UPS9_WGRAD = os.environ.get('DP_UPS9_WGRAD', '1') not in ('0', '')      # DP_UPS9_WGRAD=0: the class weight gradient everywhere (A/B runs)
+UPS9_WGRAD_TILE = (64, 64, 16)                               # (output channels, input channels) per workgroup, pixels per K tile
+_UPS9_WGRAD_NAMES = ('ups9_wgrad_kernel', 'ups9_wgrad_reduce_kernel')
+UPS9_WGRAD_BLOCKS = 512                                      # target workgroups: one round of the two resident per CU (see ups9_wgrad_gate)
+UPS9_WGRAD_GATE_MIN_PIX, UPS9_WGRAD_GATE_MIN_CH = 256, 128   # (see ups9_wgrad_gate)
+
+
+def ups9_wgrad_splits(N, Cin, Cout, H, W, splits=None):
+    """(splits, K tiles per split) of dp_ups9_wgrad: as many splits as give UPS9_WGRAD_BLOCKS workgroups, at least four K tiles each
+    (or the caller's count), none empty."""
+    bm, bn, kp = UPS9_WGRAD_TILE
+    tiles = -(-Cout // bm) * -(-Cin // bn)
+    nkt = -(-(N * H * W) // kp)
+    if splits is None:
+        splits = min(UPS9_WGRAD_BLOCKS // tiles, nkt // 4)
+    splits = max(1, min(splits, nkt))
+    tps = -(-nkt // splits)
+    return -(-nkt // tps), tps
+
+
+def ups9_wgrad_shape_ok(N, Cin, Cout, H, W, dy_img_stride, x_img_stride, dy_bytes, x_bytes, ld, splits, tiles_per_split, ws_floats,
+                        dy_ptr=0, x_ptr=0, ws_ptr=0, gw_ptr=0):
+    """The same rule as the two launchers apply before they launch (dp_ups9_wgrad_supported, csrc/ups9_wgrad.hip), argument by argument, so
+    that a launch is never refused natively after the host chose it.  H, W: the LOW resolution; strides and ld in floats, extents in bytes."""
+    if (dy_ptr & 7) or (x_ptr & 3) or (ws_ptr & 3) or (gw_ptr & 3):
+        return False
+    if min(N, Cin, Cout, H, W, splits, tiles_per_split) < 1:
+        return False
+    if ld < Cin or ws_floats < splits * 9 * Cout * ld:
+        return False
+    HW = H * W
+    npix = HW * N
+    if npix >= (1 << 29):
+        return False
+    if dy_img_stride < 4 * HW * Cout or (dy_img_stride & 1) or x_img_stride < HW * Cin:
+        return False
+    if dy_bytes < ((N - 1) * dy_img_stride + 4 * HW * Cout) * 4 or dy_bytes >= _MAX_BYTES:
+        return False
+    if x_bytes < ((N - 1) * x_img_stride + HW * Cin) * 4 or x_bytes >= _MAX_BYTES:
+        return False
+    bm, bn, kp = UPS9_WGRAD_TILE
+    nkt = -(-npix // kp)
+    if splits * tiles_per_split < nkt or (splits - 1) * tiles_per_split >= nkt:
+        return False
+    return -(-Cout // bm) * -(-Cin // bn) * splits < (1 << 31) and Cout * Cin < (1 << 31)
+
+
+def ups9_wgrad_gate(N, Cin, Cout, H, W):
+    """Shape classes on which the launch pair beat the class path it replaces (deinterleave2x2 + four conv_wgrad + ups_wfold;
+    tools/bench_ups9_wgrad.py, profiles/ups9_wgrad_gate.txt); everything else keeps the class launches.  [measured, ms per call, class
+    path -> launch pair, spread of either side at most 0.05 / 0.001: batch 256 x 256 channels 0.165 -> 0.076 (4x4), 0.387 -> 0.221 (8x8),
+    1.208 -> 0.845 (16x16); pruned 180 channels x batch 128: 0.102 -> 0.050, 0.197 -> 0.093, 0.490 -> 0.257; bedroom256's 4 images: 512 ch
+    @ 8x8 0.109 -> 0.040 (256 pixels, the fewest measured), @ 16x16 0.171 -> 0.079, 256 ch @ 32x32 0.162 -> 0.073, @ 64x64 0.382 -> 0.207,
+    128 ch @ 128x128 0.487 -> 0.232; the LDM's 6 latents: 960 ch @ 8x8 0.251 -> 0.110, 576 ch @ 16x16 0.258 -> 0.128, 384 ch @ 32x32
+    0.345 -> 0.185.  It won on every measured row by 1.4x .. 2.7x, so the gate is the measured range itself: at least 256 pixels and at
+    least 128 channels on either side; nothing narrower or smaller was timed.  Split target: 512 workgroups beat 256 and 1024 on 12 of
+    the 16 rows and lost by at most 0.01 ms elsewhere.]"""
+    return N * H * W >= UPS9_WGRAD_GATE_MIN_PIX and min(Cin, Cout) >= UPS9_WGRAD_GATE_MIN_CH
+
+
+def ups9_wgrad_wanted(N, Cin, Cout, H, W):
+    """Host gate of the nine-product weight gradient: DP_UPS9, DP_UPS9_WGRAD and the measured table.  Shapes only -- the caller's
+    tensors are checked again, strides and extents included, by ups9_wgrad_shape_ok at the launch."""
+    if not UPS9 or not UPS9_WGRAD or min(N, Cin, Cout, H, W) < 1 or N * H * W * max(Cin, 4 * Cout) * 4 >= _MAX_BYTES:
+        return False
+    return ups9_wgrad_gate(N, Cin, Cout, H, W)
+
+
+def ups9_wgrad(dy, x, gw, *, accumulate=True, splits=None):
+    """gw[Cout, Cin, 3, 3] (+)= the weight gradient of `upsample x2 -> conv3x3` from the high-resolution dy[N, Cout, 2H, 2W] and the
+    LOW-resolution x[N, Cin, H, W], in nine products per pixel.  Raises when the shape rule refuses the launch (callers ask
+    ups9_wgrad_wanted first)."""
+    sd, sx = _chk_act(dy), _chk_act(x)
+    N, Cout, H2, W2 = dy.shape
+    _, Cin, H, W = x.shape
+    assert x.shape[0] == N and H2 == 2 * H and W2 == 2 * W
+    assert gw.shape == (Cout, Cin, 3, 3) and gw.is_contiguous() and gw.dtype == _f32
+    splits, tps = ups9_wgrad_splits(N, Cin, Cout, H, W, splits)
+    n = splits * 9 * Cout * Cin
+    ws = _workspace(n, dy.device)
+    p = L.Ups9WgradParams()
+    p.dy, p.x, p.ws, p.gw = _p(dy), _p(x), _p(ws), _p(gw)
+    p.dy_img_stride, p.x_img_stride, p.ws_floats = sd, sx, ws.numel()
+    p.dy_bytes, p.x_bytes = _extent_bytes(dy), _extent_bytes(x)
+    p.N, p.Co, p.Ci, p.H, p.W = N, Cout, Cin, H, W
+    p.splits, p.tiles_per_split, p.ld, p.accumulate = splits, tps, Cin, 1 if accumulate else 0
+    ok = ups9_wgrad_shape_ok(N, Cin, Cout, H, W, sd, sx, p.dy_bytes, p.x_bytes, p.ld, splits, tps, p.ws_floats, dy.data_ptr(),
+                             x.data_ptr(), ws.data_ptr(), gw.data_ptr())
+    if not ok:
+        raise ValueError('dp_ups9_wgrad does not take this launch (ups9_wgrad_shape_ok)')
+    rc = _run(lambda: _lib().dp_ups9_wgrad(C.byref(p), _stream()), _UPS9_WGRAD_NAMES[0], 18.0 * Cout * Cin * N * H * W,
+              4.0 * (dy.numel() + x.numel() + n))
+    assert rc != 1, 'host shape rule and dp_ups9_wgrad disagree (hipErrorInvalidValue for a launch ups9_wgrad_shape_ok takes)'
+    L.check(rc, 'dp_ups9_wgrad')
+    L.check(_run(lambda: _lib().dp_ups9_wgrad_reduce(C.byref(p), _stream()), _UPS9_WGRAD_NAMES[1], 0.0, 4.0 * (n + gw.numel())),
+            'dp_ups9_wgrad_reduce')
+    return gw
+
+
 _ws_cache = {}
 WGRAD_BLOCKS = 1024         # target workgroups per wgrad launch (256 CUs x 4 resident workgroups)
 WGRAD_MIN_PIX = int(os.environ.get('DP_WGRAD_MIN_PIX', '128'))      # fewest pixels per split-K slice of a weight gradient

@@ -363,6 +363,24 @@ typedef struct dp_ups9_fwd_params {
     int ldu, N, M, K, H, W;
 } dp_ups9_fwd_params;
 int dp_ups9_fwd(const dp_ups9_fwd_params* p, void* stream);
+/* The WEIGHT gradient of the same convolution in nine products (csrc/ups9_wgrad.hip), two launches:
+ * dp_ups9_wgrad: ws[split][a][b][co][ci] = sum over the split's pixels of dM[n][co][a][b][i][j] V[n][ci][a][b][i][j], dM = A D A^T of
+ * the 2x2 block D of the high-resolution dy[N][Co][2H][2W] at rows 2i, 2i+1 / columns 2j, 2j+1 (A = [1 0; 1 1; 0 1]), V as in
+ * dp_ups9_fwd from the low-resolution x[N][Ci][H][W].  K tiles of 16 low-resolution pixels numbered over all images; split s takes the
+ * tiles [s * tiles_per_split, (s + 1) * tiles_per_split): splits * tiles_per_split covers all of them and no split is empty.
+ * dp_ups9_wgrad_reduce: dU = the splits added in ascending order, gw[Co][Ci][3][3] (+)= G^T dU G (accumulate != 0: +=).
+ * dy / x: contiguous images at dy_img_stride / x_img_stride floats, dy 8-byte aligned and dy_img_stride even; dy_bytes / x_bytes: readable
+ * extents, below 2 GiB.  ws: ws_floats >= splits * 9 * Co * ld floats, row pitch ld >= Ci.  No atomics, one fixed-order sum per output:
+ * the same bits from run to run.  Both launchers check all of this themselves (dp_ups9_wgrad_supported, csrc/ups9_wgrad.hip) and return
+ * hipErrorInvalidValue, launching nothing, for what they do not take (ops.ups9_wgrad_shape_ok is the host's restatement of that rule). */
+typedef struct dp_ups9_wgrad_params {
+    const float* dy; const float* x; float* ws; float* gw;
+    long long dy_img_stride, x_img_stride, ws_floats;
+    unsigned dy_bytes, x_bytes;
+    int N, Co, Ci, H, W, splits, tiles_per_split, ld, accumulate;
+} dp_ups9_wgrad_params;
+int dp_ups9_wgrad(const dp_ups9_wgrad_params* p, void* stream);
+int dp_ups9_wgrad_reduce(const dp_ups9_wgrad_params* p, void* stream);
 
 /* Taylor-importance reductions  (ddpm_exp/torch_pruning/importance.py:375-434).
  * Weight viewed as [R][C][T]; dim = 0: out[r] = sum_{c,t} f(w*g); dim = 1: out[c] = sum_{r,t} f(w*g);
