@@ -234,6 +234,9 @@ SIGNATURES = {
     'dp_vq_blocks': [_ll],
     'dp_vq_quantize': [_vp, _ll, _i, _i, _ll, _vp, _i, _vp, _ll, _vp, _vp, _vp],
     'dp_vq_loss': [_vp, _i, C.c_double, _vp, _vp],
+    'dp_gaussian_posterior_ws': [_i, _ll],
+    'dp_gaussian_posterior': [_vp, _ll, _i, _ll, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'dp_tile_blend': [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp],
     'dp_replay_build': [_vp, C.POINTER(C.c_void_p)],
     'dp_replay_launch': [_vp, _vp, _vp],
     'dp_replay_info': [_vp, C.POINTER(C.c_int)],
@@ -262,7 +265,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = C.c_longlong if name in ('dp_launch_count', 'dp_ssim_workspace', 'dp_select_smallest_workspace') else C.c_int
+        fn.restype = C.c_longlong if name in ('dp_launch_count', 'dp_ssim_workspace', 'dp_select_smallest_workspace', 'dp_gaussian_posterior_ws') else C.c_int
     _lib = lib
     return lib
 

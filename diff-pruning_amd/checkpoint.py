@@ -356,6 +356,37 @@ def save_vq(model, directory, safe_serialization=False):
         torch.save(sd, os.path.join(directory, _UNET_WEIGHTS[1]))
 
 
+def load_vae(directory, subfolder=None):
+    """AutoencoderKL.from_pretrained: `directory` (or its `subfolder`, or its `vae/` folder) holds config.json + the weight file;
+    deprecated attention names are converted as modeling_utils.py:809-851 does."""
+    from .vae import AutoencoderKL
+    d = os.path.join(directory, subfolder) if subfolder else directory
+    if not os.path.exists(os.path.join(d, 'config.json')) and os.path.exists(os.path.join(d, 'vae', 'config.json')):
+        d = os.path.join(d, 'vae')
+    raw = _read_json(os.path.join(d, 'config.json'))
+    if raw.get('_class_name', 'AutoencoderKL') != 'AutoencoderKL':
+        raise ValueError('%s holds a %s, not an AutoencoderKL' % (d, raw['_class_name']))
+    model = AutoencoderKL(**{k: v for k, v in raw.items() if not k.startswith('_')})
+    model.load_state_dict(convert_deprecated_attention_keys(_load_weights(d)), strict=True)
+    return model.eval()
+
+
+def save_vae(model, directory, safe_serialization=False):
+    """AutoencoderKL.save_pretrained layout (config.json + diffusion_pytorch_model.bin, or .safetensors)."""
+    os.makedirs(directory, exist_ok=True)
+    cfg = dict(_config_dict(model), _class_name='AutoencoderKL', _diffusers_version=DIFFUSERS_VERSION)
+    _write_json(os.path.join(directory, 'config.json'), cfg)
+    sd = {k: v.detach().to('cpu').contiguous() for k, v in model.state_dict().items()}
+    if safe_serialization:
+        from safetensors.torch import save_file
+        save_file(sd, os.path.join(directory, _UNET_WEIGHTS[0]))
+    else:
+        torch.save(sd, os.path.join(directory, _UNET_WEIGHTS[1]))
+
+
+_FIRST_STAGES = {'VQModel': (load_vq, save_vq), 'AutoencoderKL': (load_vae, save_vae)}
+
+
 def load_pipeline(cls, directory):
     from . import diffusion
     index = _read_json(os.path.join(directory, 'model_index.json'))
@@ -365,7 +396,10 @@ def load_pipeline(cls, directory):
         raise NotImplementedError('scheduler class %s' % sched_name)
     parts = dict(unet=load_unet(directory, 'unet'), scheduler=load_scheduler(sched_cls, directory, 'scheduler'))
     if 'vqvae' in index:                                 # LDMPipeline (pipeline_latent_diffusion_uncond.py)
-        parts['vqvae'] = load_vq(directory, 'vqvae')
+        name = index['vqvae'][1]                         # the component's own class: VQModel, or AutoencoderKL
+        if name not in _FIRST_STAGES:
+            raise NotImplementedError('first-stage class %s' % name)
+        parts['vqvae'] = _FIRST_STAGES[name][0](directory, 'vqvae')
     return cls(**parts)
 
 
@@ -373,8 +407,9 @@ def save_pipeline(pipeline, directory, safe_serialization=False):
     index = dict(_class_name=type(pipeline).__name__, _diffusers_version=DIFFUSERS_VERSION,
                  scheduler=['diffusers', type(pipeline.scheduler).__name__], unet=['diffusers', 'UNet2DModel'])
     if getattr(pipeline, 'vqvae', None) is not None:
-        index['vqvae'] = ['diffusers', 'VQModel']
-        save_vq(pipeline.vqvae, os.path.join(directory, 'vqvae'), safe_serialization)
+        name = type(pipeline.vqvae).__name__
+        index['vqvae'] = ['diffusers', name]
+        _FIRST_STAGES[name][1](pipeline.vqvae, os.path.join(directory, 'vqvae'), safe_serialization)
     _write_json(os.path.join(directory, 'model_index.json'), index)
     save_unet(pipeline.unet, os.path.join(directory, 'unet'), safe_serialization)
     save_scheduler(pipeline.scheduler, os.path.join(directory, 'scheduler'))
@@ -463,6 +498,20 @@ def vq_config_from_ldm(ddconfig, embed_dim, n_embed):
                 block_out_channels=[ddconfig['ch'] * m for m in mult], layers_per_block=ddconfig['num_res_blocks'], act_fn='silu',
                 latent_channels=ddconfig['z_channels'], sample_size=ddconfig.get('resolution', 256), num_vq_embeddings=n_embed,
                 norm_num_groups=32, vq_embed_dim=embed_dim, scaling_factor=0.18215)
+
+
+def kl_config_from_ldm(ddconfig, embed_dim):
+    """AutoencoderKL kwargs equivalent to an ldm_exp KL first stage (first_stage_config.params: ddconfig, embed_dim;
+    ldm/models/autoencoder.py:285-310).  `double_z` is required; ldm_exp's quant_conv maps 2 z_channels -> 2 embed_dim and its
+    post_quant_conv embed_dim -> z_channels, which is the Diffusers layout only when embed_dim == z_channels (every shipped config)."""
+    if not ddconfig.get('double_z', False):
+        raise NotImplementedError('a first stage without double_z is a VQ autoencoder, not KL (vq_config_from_ldm)')
+    if embed_dim != ddconfig['z_channels']:
+        raise NotImplementedError('embed_dim %r != z_channels %r is not an AutoencoderKL layout' % (embed_dim, ddconfig['z_channels']))
+    cfg = vq_config_from_ldm(dict(ddconfig, double_z=False), embed_dim, 0)       # the same refusals, in the same words
+    for k in ('num_vq_embeddings', 'vq_embed_dim'):
+        del cfg[k]
+    return cfg
 
 
 # --------------------------------------------------------------------------------------------------------

@@ -30,6 +30,7 @@ import torch.nn as nn
 
 from . import ops
 from .sweep import Pipeline, dist_active, flatten_grads
+from .vae import AutoencoderKL
 
 CFG_SHARED_STEM = not os.environ.get('DP_NO_CFG_SHARED_STEM')
 
@@ -456,14 +457,20 @@ def decode_first_stage(vq, z, scale_factor=1.0, force_not_quantize=False):
     z = z.detach().to(torch.float32).contiguous()
     if scale_factor != 1.0:
         z = ops.axpby(z, float(1.0 / scale_factor), torch.empty_like(z), 0.0)     # `1. / self.scale_factor * z` in fp32
+    if isinstance(vq, AutoencoderKL):                    # AutoencoderKL.decode takes no force_not_quantize (ddpm.py:757-760)
+        return vq.decode(z).sample
     return vq.decode(z, force_not_quantize=force_not_quantize).sample
 
 
 @torch.no_grad()
-def encode_first_stage(vq, images, scale_factor=1.0):
+def encode_first_stage(vq, images, scale_factor=1.0, generator=None):
     """LatentDiffusion.encode_first_stage + get_first_stage_encoding (ldm/models/diffusion/ddpm.py:826-863, 542-551) for the VQ
     first stage: VQModelInterface.encode -- encoder, quant_conv, NO quantisation -- times scale_factor.  `vq`: a VQModel (vq.py).
-    Returns the latents [N, z, H / f, W / f] the finetune step diffuses (ldm_train.LdmFinetuneEngine.step_images)."""
+    Returns the latents [N, z, H / f, W / f] the finetune step diffuses (ldm_train.LdmFinetuneEngine.step_images).
+    On an AutoencoderKL (vae.py) the encoding is the posterior's sample (noise drawn on the host from `generator`, then moved, as
+    ldm_exp's DiagonalGaussianDistribution.sample does) times scale_factor, in the posterior kernel's one pass."""
+    if isinstance(vq, AutoencoderKL):
+        return vq.encode(images).latent_dist.sample(generator=generator, host_noise=True, scale=scale_factor)
     z = vq.encode(images).latents
     if scale_factor != 1.0:
         z = ops.axpby(z.contiguous(), float(scale_factor), torch.empty_like(z), 0.0)      # `self.scale_factor * z` in fp32

@@ -2216,6 +2216,75 @@ def unipc_step(e, x_pred, coef, pc=0, pp=1, predict_x0=True, x_last=None, hist=(
     return out, x_c, m_new
 
 
+VAE_MAX_BLOCKS = 4096                # DP_VAE_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, grid-stride beyond
+POSTERIOR_OUTPUTS = ('logvar', 'std', 'var', 'z', 'kl')
+
+
+def gaussian_posterior(moments, noise=None, scale=1.0, logvar=False, std=False, var=False, z=False, kl=False):
+    """DiagonalGaussianDistribution in one pass (dp_gaussian_posterior, csrc/vae.hip) over moments [N, 2C, H, W] (inner strides
+    contiguous, the image stride free): lv = clamp(logvar, -30, 20), std = exp(0.5 lv), var = exp(lv), z = scale * (mean + std * noise)
+    with every operation rounded on its own (scale == 1 skips the multiply), kl[n] = 0.5 sum(mean^2 + var - 1 - lv) summed in double.
+    Each of logvar / std / var / z / kl is False (skipped), True (allocated here) or the contiguous fp32 tensor to fill; `z` may be
+    `noise` itself, no other output may share memory with an input.  Returns {name: tensor} of the outputs asked for."""
+    s = _chk_act(moments)
+    N, C2, H, W = moments.shape
+    assert C2 % 2 == 0 and N >= 1 and C2 * H * W > 0, 'gaussian_posterior: moments [N, 2C, H, W]'
+    chw = (C2 // 2) * H * W
+    _extent_bytes(moments)
+    given = dict(logvar=logvar, std=std, var=var, z=z, kl=kl)
+    out = {}
+    for name in POSTERIOR_OUTPUTS:
+        t = given[name]
+        if t is False or t is None:
+            continue
+        shape = (N,) if name == 'kl' else (N, C2 // 2, H, W)
+        if t is True:
+            t = torch.empty(shape, dtype=_f32, device=moments.device)
+        assert t.dtype == _f32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape, 'gaussian_posterior: output %s' % name
+        _checked_bytes(4 * t.numel())
+        out[name] = t
+    ws = None
+    if 'z' in out:
+        assert noise is not None and noise.dtype == _f32 and noise.is_cuda and noise.is_contiguous() and \
+            tuple(noise.shape) == (N, C2 // 2, H, W), 'gaussian_posterior: a sample needs noise [N, C, H, W]'
+    if 'kl' in out:
+        ws = torch.empty(int(_lib().dp_gaussian_posterior_ws(N, chw)), dtype=torch.float64, device=moments.device)
+    L.check(_lib().dp_gaussian_posterior(_p(moments), s, N, chw, _p(noise) if 'z' in out else None, float(scale), _p(out.get('logvar')),
+                                         _p(out.get('std')), _p(out.get('var')), _p(out.get('z')), _p(out.get('kl')), _p(ws), _stream()),
+            'dp_gaussian_posterior')
+    return out
+
+
+def tile_blend(b, above=None, left=None, blend_extent=0, out=None, oy=0, ox=0, row_limit=None):
+    """One tile of a tiled encode / decode in one launch (dp_tile_blend, csrc/vae.hip): AutoencoderKL.blend_v with the tile `above`,
+    then blend_h with the tile to the `left` (both already blended), written back into `b`, and b[:, :, :row_limit, :row_limit] into
+    the canvas `out` at (oy, ox).  All tensors contiguous fp32 [N, C, ., .].  Returns b."""
+    for t in (b, above, left, out):
+        assert t is None or (t.dtype == _f32 and t.is_cuda and t.dim() == 4 and t.is_contiguous()), 'tile_blend: contiguous fp32 [N, C, H, W]'
+        if t is not None:
+            assert tuple(t.shape[:2]) == tuple(b.shape[:2])
+            _extent_bytes(t)
+    N, Cc, Hb, Wb = b.shape
+    Ha = ev = Wl = eh = 0
+    if above is not None:
+        assert above.shape[3] == Wb, 'tile_blend: the tile above has another width'
+        Ha = above.shape[2]
+        ev = min(Ha, Hb, int(blend_extent))
+    if left is not None:
+        assert left.shape[2] == Hb, 'tile_blend: the tile to the left has another height'
+        Wl = left.shape[3]
+        eh = min(Wl, Wb, int(blend_extent))
+    if ev < 1:
+        above = None
+    if eh < 1:
+        left = None
+    Hout, Wout = (out.shape[2], out.shape[3]) if out is not None else (0, 0)
+    rl = int(row_limit) if row_limit is not None else max(Hb, Wb)
+    L.check(_lib().dp_tile_blend(_p(b), N * Cc, Hb, Wb, _p(above), Ha, ev, _p(left), Wl, eh, _p(out), Hout, Wout, int(oy), int(ox), rl,
+                                 _stream()), 'dp_tile_blend')
+    return b
+
+
 # --------------------------------------------------------------------------------------------------
 # LDM transformer-block glue (channel-major tokens [N, C, H, W] == [N][C][T])
 # --------------------------------------------------------------------------------------------------

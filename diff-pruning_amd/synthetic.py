@@ -44,6 +44,15 @@ VQ_F4_CFG = dict(in_channels=3, out_channels=3, down_block_types=['DownEncoderBl
 VQ_TINY_CFG = dict(VQ_F4_CFG, down_block_types=['DownEncoderBlock2D'] * 2, up_block_types=['UpDecoderBlock2D'] * 2,
                    block_out_channels=[32, 64], layers_per_block=1, sample_size=16, num_vq_embeddings=64, norm_num_groups=8)
 
+# KL-f8 first stage (kl-f8 / configs/autoencoder/autoencoder_kl_32x32x4.yaml: ch 128, ch_mult (1, 2, 4, 4), 2 res blocks, z 4) as a
+# Diffusers AutoencoderKL config
+KL_F8_CFG = dict(in_channels=3, out_channels=3, down_block_types=['DownEncoderBlock2D'] * 4, up_block_types=['UpDecoderBlock2D'] * 4,
+                 block_out_channels=[128, 256, 512, 512], layers_per_block=2, act_fn='silu', latent_channels=4, norm_num_groups=32,
+                 sample_size=256, scaling_factor=0.18215)
+# reduced width for full-tensor fixtures: tiles of 16 pixels / 8 latents
+KL_TINY_CFG = dict(KL_F8_CFG, down_block_types=['DownEncoderBlock2D'] * 2, up_block_types=['UpDecoderBlock2D'] * 2,
+                   block_out_channels=[16, 32], layers_per_block=1, norm_num_groups=8, sample_size=16)
+
 
 def _rng(name, seed):
     return np.random.default_rng([zlib.crc32(name.encode()), seed])

@@ -706,6 +706,35 @@ int dp_vq_quantize(const float* z, long long z_bs, int D, int HW, long long P, c
                    long long* idx, double* partial, void* stream);
 int dp_vq_loss(const double* partial, int nblocks, double scale, float* loss, void* stream);
 
+/* The posterior of the KL autoencoder (csrc/vae.hip; diffusers DiagonalGaussianDistribution, vae.py:384-428) in one pass over the
+ * moments [N][2 chw]: per image (image stride m_stride floats) the first chw floats are the mean, the next chw the log-variance.
+ *   lv = clamp(logvar, -30, 20) (a NaN stays a NaN);  std = exp(0.5 lv);  var = exp(lv);
+ *   z = scale * (mean + std * noise), each operation rounded on its own, the multiply by scale skipped when scale == 1;
+ *   kl[n] = (float)(0.5 * sum_i (mean^2 + var - 1 - lv)), summed in double in a fixed order (two calls give the same bits).
+ * Outputs logvar / std / var / z [N][chw] (contiguous) and kl [N] are optional: a NULL pointer skips one.  z needs noise [N][chw];
+ * kl needs kl_ws, dp_gaussian_posterior_ws(N, chw) doubles (per-block partial sums, combined by a second launch).
+ * No output may overlap an input or another output, except that z may be noise itself (a lane reads its elements before it writes
+ * them): any other overlap is hipErrorInvalidValue and nothing is launched.  16-byte accesses when chw % 4 == 0, m_stride % 4 == 0 and
+ * every pointer in use is 16-byte aligned, 4-byte accesses otherwise; at most DP_VAE_MAX_BLOCKS blocks of 256 lanes, grid-stride beyond. */
+#define DP_VAE_MAX_BLOCKS 4096
+long long dp_gaussian_posterior_ws(int N, long long chw);
+int dp_gaussian_posterior(const float* moments, long long m_stride, int N, long long chw, const float* noise, float scale,
+                          float* logvar, float* std, float* var, float* z, float* kl, double* kl_ws, void* stream);
+
+/* One tile of a tiled encode / decode blended into its neighbours and cropped into the canvas, in one launch (csrc/vae.hip;
+ * AutoencoderKL.blend_v, blend_h, the crop and the two torch.cat of autoencoder_kl.py:198-208, 236-249, 285-298).
+ * b [planes][Hb][Wb] is updated in place; a [planes][Ha][Wb] is the (already blended) tile above, l [planes][Hb][Wl] the one to the
+ * left, either may be NULL.  With ev / eh the blend extents the host formed (min(Ha, Hb, extent), min(Wl, Wb, extent)):
+ *   v = b[y][x]
+ *   a and y < ev:  v = a[Ha - ev + y][x] * w0(y, ev) + v * w1(y, ev)
+ *   l and x < eh:  v = l[y][Wl - eh + x] * w0(x, eh) + v * w1(x, eh)
+ * w1(k, e) = (float)(k / e) and w0(k, e) = (float)(1 - k / e) evaluated in double; every product and sum rounded on its own.
+ * v is stored to b[y][x] and, where y < row_limit and x < row_limit, to out[plane][oy + y][ox + x] of the canvas
+ * [planes][Hout][Wout] (out may be NULL).  A crop that leaves the canvas, an extent outside its tiles or b overlapping another
+ * buffer is hipErrorInvalidValue and nothing is launched. */
+int dp_tile_blend(float* b, int planes, int Hb, int Wb, const float* a, int Ha, int ev, const float* l, int Wl, int eh,
+                  float* out, int Hout, int Wout, int oy, int ox, int row_limit, void* stream);
+
 /* Native replay list (csrc/replay.hip): re-issue the kernels / memsets of a stream-captured step from a C loop.  The
  * reference's loop re-launches ~700 ATen kernels per timestep from Python (ddpm_prune.py:94-106); here one timestep is captured
  * once into a hipGraph (never instantiated: hipGraphLaunch of these graphs costs more host time than eager launches on this
