@@ -113,6 +113,10 @@ class DpmSolverCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sigma_s', 'alpha_s', 'kx', 'k0', 'k1', 'k2', 'ir0', 'ir1', 'q', 'iq')]
 
 
+class X0Coef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'range', 'c0', 'c1', 'cz')]
+
+
 class UniPCCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sigma_s', 'alpha_s', 'c_cx', 'c_c0', 'c_cB', 'c_rk1', 'c_rk2', 'c_rho1', 'c_rho2', 'c_rho_last',
                                          'p_cx', 'p_c0', 'p_cB', 'p_rk1', 'p_rk2', 'p_rho1', 'p_rho2')]
@@ -210,6 +214,10 @@ SIGNATURES = {
     'dp_cfg_denoise_step': [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp],
     'dp_dpm_solver_step': [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(DpmSolverCoef), _vp, _vp, _ll, _vp],
     'dp_unipc_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(UniPCCoef), _vp, _vp, _vp, _ll, _vp],
+    'dp_x0_abs_quantile_workspace': [_ll, _ll],
+    'dp_x0_abs_quantile': [_vp, _vp, _ll, _ll, _i, _f, _f, _ll, _ll, _f, _f, _i, _vp, _vp, _vp],
+    'dp_x0_step': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(X0Coef), _vp, _vp, _ll, _ll, _vp],
+    'dp_x0_threshold_step': [_vp, _vp, _vp, _i, _i, _i, C.POINTER(X0Coef), _ll, _ll, _f, _f, _vp, _vp, _vp, _ll, _ll, _vp],
     'dp_dropout_apply': [_vp, _ll, _vp, _ll, _i, _ll, _dr, _vp],
     'dp_dropout_mask': [_vp, _ll, _ll, _dr, _vp],
     'dp_layernorm_fwd': [_vp, _ll, _vp, _vp, _i, _i, _i, _f, _vp, _ll, _vp, _vp],
@@ -265,7 +273,8 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = C.c_longlong if name in ('dp_launch_count', 'dp_ssim_workspace', 'dp_select_smallest_workspace', 'dp_gaussian_posterior_ws') else C.c_int
+        fn.restype = C.c_longlong if name in ('dp_launch_count', 'dp_ssim_workspace', 'dp_select_smallest_workspace', 'dp_gaussian_posterior_ws',
+                                               'dp_x0_abs_quantile_workspace') else C.c_int
     _lib = lib
     return lib
 

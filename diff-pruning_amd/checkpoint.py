@@ -317,8 +317,9 @@ def load_scheduler(cls, directory, subfolder=None):
     if not os.path.exists(os.path.join(d, 'scheduler_config.json')) and os.path.exists(os.path.join(d, 'scheduler')):
         d = os.path.join(d, 'scheduler')
     cfg = {k: v for k, v in _read_json(os.path.join(d, 'scheduler_config.json')).items() if not k.startswith('_')}
-    if cfg.get('thresholding') or cfg.get('trained_betas') is not None:
-        raise NotImplementedError('thresholding / trained_betas schedulers are not on the hot path')
+    if cfg.get('trained_betas') is not None:
+        raise NotImplementedError('trained_betas schedulers are not on the hot path')
+    # `thresholding` is the class's to take or refuse: DDPMScheduler and DDIMScheduler carry it, the multistep solvers raise
     import inspect
     accepted = set(inspect.signature(cls.__init__).parameters) - {'self'}
     return cls(**{k: v for k, v in cfg.items() if k in accepted})

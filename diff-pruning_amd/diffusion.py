@@ -82,6 +82,21 @@ class _SchedulerBase:
             self._acp_dev[device] = t
         return t
 
+    _PREDICTION_TYPES = ('epsilon', 'sample', 'v_prediction')
+
+    def _x0_treatment(self):
+        """(treat, host scalars) of step 3 / 4 of the reference's `step`: thresholding wins over clip_sample."""
+        cfg = self.config
+        if cfg.thresholding:
+            return ops.X0_TREAT_THRESHOLD, dict(ratio=cfg.dynamic_thresholding_ratio, max_value=cfg.sample_max_value)
+        if cfg.clip_sample:
+            return ops.X0_TREAT_CLIP, dict(range=cfg.clip_sample_range)
+        return ops.X0_TREAT_NONE, {}
+
+    def _threshold_sample(self, sample):
+        """scheduling_ddpm.py:278-310 for a caller's own [B, C, H, W] tensor (ops.dynamic_threshold)."""
+        return ops.dynamic_threshold(sample.contiguous(), self.config.dynamic_thresholding_ratio, self.config.sample_max_value)
+
     def add_noise(self, original_samples, noise, timesteps):
         if original_samples.device.type != 'cuda':
             raise RuntimeError('add_noise runs on the HIP kernels: tensors must live on a cuda device')
@@ -97,11 +112,22 @@ class DDPMSchedulerOutput:
 
 
 class DDPMScheduler(_SchedulerBase):
+    """scheduling_ddpm.py:92-467 for epsilon, `sample` and `v_prediction` models, with clip_sample or dynamic thresholding
+    (`thresholding`, `dynamic_thresholding_ratio`, `sample_max_value`: per image s = clamp(quantile(|x0|, ratio), min=1,
+    max=sample_max_value), x0 = clamp(x0, -s, s) / s).  With the default sample_max_value = 1.0 the reference's clamp makes
+    s == 1 for every image: thresholding is then a clip to [-1, 1], and the option only acts with sample_max_value > 1.
+    Not carried (NotImplementedError): `trained_betas`, models that predict a variance, the learned variance types."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'variance_type', 'clip_sample',
+                    'prediction_type', 'clip_sample_range', 'thresholding', 'dynamic_thresholding_ratio', 'sample_max_value')
+
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear',
-                 variance_type='fixed_small', clip_sample=True, prediction_type='epsilon', clip_sample_range=1.0):
+                 variance_type='fixed_small', clip_sample=True, prediction_type='epsilon', clip_sample_range=1.0,
+                 thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0):
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, variance_type=variance_type, clip_sample=clip_sample,
-                                      prediction_type=prediction_type, clip_sample_range=clip_sample_range)
+                                      prediction_type=prediction_type, clip_sample_range=clip_sample_range,
+                                      thresholding=thresholding, dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                                      sample_max_value=sample_max_value)
         self._init_tables(num_train_timesteps, beta_start, beta_end, beta_schedule)
         self.one = torch.tensor(1.0)
         self.variance_type = variance_type
@@ -112,9 +138,7 @@ class DDPMScheduler(_SchedulerBase):
     @classmethod
     def from_config(cls, config):
         d = vars(config) if not isinstance(config, dict) else config
-        keys = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'variance_type', 'clip_sample',
-                'prediction_type', 'clip_sample_range')
-        return cls(**{k: d[k] for k in keys if k in d})
+        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -168,11 +192,14 @@ class DDPMScheduler(_SchedulerBase):
         raise NotImplementedError('variance_type %s needs a model that predicts the variance' % vt)
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, variance_noise=None):
-        """scheduling_ddpm.py:312-406, epsilon prediction.  The coefficients are 0-d fp32 tensors computed on the host in
-        the reference's operation order; the per-element update runs in one HIP kernel (dp_ddpm_step).
+        """scheduling_ddpm.py:312-406.  The coefficients are 0-d fp32 tensors computed on the host in the reference's operation
+        order.  An epsilon model without thresholding runs in one HIP kernel (dp_ddpm_step), as it always has; a `sample` or
+        `v_prediction` model, or dynamic thresholding, goes through ops.x0_step (csrc/threshold.hip: one launch where an image's
+        row fits in LDS) and returns the treated x0 as `pred_original_sample`.
         `variance_noise` (extension): caller-supplied noise instead of a draw from `generator` (parity tests)."""
-        if self.config.prediction_type != 'epsilon':
-            raise NotImplementedError('only epsilon prediction is on the hot path')
+        pt = self.config.prediction_type
+        if pt not in self._PREDICTION_TYPES:
+            raise ValueError('prediction_type given as %s must be one of `epsilon`, `sample` or `v_prediction`  for the DDPMScheduler.' % pt)
         if model_output.shape[1] != sample.shape[1]:
             raise NotImplementedError('learned-variance models are not part of this path')
         t = int(timestep)
@@ -195,6 +222,15 @@ class DDPMScheduler(_SchedulerBase):
                 sigma = float(self._get_variance(t) ** 0.5)
             else:
                 raise NotImplementedError('variance_type %s' % self.variance_type)
+        if pt != 'epsilon' or self.config.thresholding:
+            treat, c = self._x0_treatment()
+            c.update(sa=float(a_t ** 0.5), sb=float(b_t ** 0.5), c0=float(c_x0), c1=float(c_xt), cz=sigma)
+            x0 = torch.empty_like(sample, memory_format=torch.contiguous_format)
+            prev, x0, _ = ops.x0_step(sample.contiguous(), model_output.contiguous(), ops.X0_MODE_DDPM, ops.X0_PRED[pt], treat, c,
+                                      z=None if noise is None else noise.contiguous(), x0_out=x0)
+            if not return_dict:
+                return (prev,)
+            return DDPMSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
         prev = ops.ddpm_step(sample.contiguous(), model_output.contiguous(), float(a_t ** 0.5), float(b_t ** 0.5),
                              float(c_x0), float(c_xt), sigma, None if noise is None else noise.contiguous(),
                              clip=self.config.clip_sample, clip_range=self.config.clip_sample_range)
@@ -210,15 +246,26 @@ class DDIMSchedulerOutput:
 
 
 class DDIMScheduler(_SchedulerBase):
+    """scheduling_ddim.py:78-440 (reference-modified: skip_type) for epsilon, `sample` and `v_prediction` models, with
+    clip_sample or dynamic thresholding (`thresholding`, `dynamic_thresholding_ratio`, `sample_max_value`: per image
+    s = clamp(quantile(|x0|, ratio), min=1, max=sample_max_value), x0 = clamp(x0, -s, s) / s) and `use_clipped_model_output`.
+    With the default sample_max_value = 1.0 the reference's clamp makes s == 1 for every image: thresholding is then a clip to
+    [-1, 1], and the option only acts with sample_max_value > 1.  Not carried (NotImplementedError): `trained_betas`."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'clip_sample', 'set_alpha_to_one',
+                    'steps_offset', 'prediction_type', 'skip_type', 'clip_sample_range', 'thresholding',
+                    'dynamic_thresholding_ratio', 'sample_max_value')
+
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear',
                  skip_type='uniform', clip_sample=True, set_alpha_to_one=True, steps_offset=0, prediction_type='epsilon',
-                 clip_sample_range=1.0):
-        if prediction_type != 'epsilon':
-            raise NotImplementedError('only epsilon prediction is on the hot path')
+                 clip_sample_range=1.0, thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0):
+        if prediction_type not in self._PREDICTION_TYPES:
+            raise ValueError('prediction_type given as %s must be one of `epsilon`, `sample`, or `v_prediction`' % prediction_type)
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, clip_sample=clip_sample,
                                       set_alpha_to_one=set_alpha_to_one, steps_offset=steps_offset,
-                                      prediction_type=prediction_type, clip_sample_range=clip_sample_range)
+                                      prediction_type=prediction_type, clip_sample_range=clip_sample_range,
+                                      thresholding=thresholding, dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                                      sample_max_value=sample_max_value)
         self.config.skip_type = skip_type            # the reference registers skip_type in the config (scheduling_ddim.py:122)
         self._init_tables(num_train_timesteps, beta_start, beta_end, beta_schedule)
         self.skip_type = skip_type
@@ -229,9 +276,7 @@ class DDIMScheduler(_SchedulerBase):
     @classmethod
     def from_config(cls, config):
         d = vars(config) if not isinstance(config, dict) else config
-        keys = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'clip_sample', 'set_alpha_to_one',
-                'steps_offset', 'prediction_type', 'skip_type', 'clip_sample_range')
-        return cls(**{k: d[k] for k in keys if k in d})
+        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -261,10 +306,12 @@ class DDIMScheduler(_SchedulerBase):
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True):
+        """scheduling_ddim.py:270-390.  An epsilon model without thresholding and without `use_clipped_model_output` runs in one HIP
+        kernel (dp_ddim_step), as it always has; every other step goes through ops.x0_step (csrc/threshold.hip: one launch where
+        an image's row fits in LDS), with the host scalars as 0-d fp32 tensor arithmetic in the reference's order, and returns
+        the treated x0 as `pred_original_sample`."""
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        if use_clipped_model_output:
-            raise NotImplementedError('use_clipped_model_output is not used by the reference scripts')
         t = int(timestep)
         prev_t = t - self.config.num_train_timesteps // self.num_inference_steps      # reference quirk kept
         a_t = self.alphas_cumprod[t]
@@ -275,6 +322,19 @@ class DDIMScheduler(_SchedulerBase):
             if variance_noise is None:
                 variance_noise = randn_tensor(model_output.shape, generator=generator, device=model_output.device,
                                               dtype=model_output.dtype)
+        pt = self.config.prediction_type
+        if pt != 'epsilon' or self.config.thresholding or use_clipped_model_output:
+            treat, c = self._x0_treatment()
+            std_dev_t = eta * self._get_variance(t, prev_t) ** 0.5
+            c.update(sa=float(a_t ** 0.5), sb=float((1 - a_t) ** 0.5), c0=float(a_prev ** 0.5),
+                     c1=float((1 - a_prev - std_dev_t ** 2) ** 0.5), cz=std)
+            x0 = torch.empty_like(sample, memory_format=torch.contiguous_format)
+            prev, x0, _ = ops.x0_step(sample.contiguous(), model_output.contiguous(), ops.X0_MODE_DDIM, ops.X0_PRED[pt], treat, c,
+                                      z=variance_noise.contiguous() if eta > 0 else None, x0_out=x0,
+                                      reclip=bool(use_clipped_model_output))
+            if not return_dict:
+                return (prev,)
+            return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
         prev = ops.ddim_step(sample.contiguous(), model_output.contiguous(), float(a_t), float(a_prev), std,
                              variance_noise if eta > 0 else None, clip=self.config.clip_sample,
                              clip_range=self.config.clip_sample_range)
@@ -795,11 +855,12 @@ class DDIMPipeline(_PipelineBase):
         image = randn_tensor(shape, generator=generator, device=self.device, dtype=self.unet.dtype)
         self.scheduler.set_timesteps(num_inference_steps)
         ts = [int(t) for t in self.scheduler.timesteps.tolist()]
+        extra = {'use_clipped_model_output': True} if use_clipped_model_output else {}      # pipeline_ddim.py:113-115
         fwd = _sampling_forward(self.unet, shape, len(ts))
         try:
             for t in self.progress_bar(ts):
                 model_output = fwd(image, t)
-                image = self.scheduler.step(model_output, t, image, eta=eta, generator=generator).prev_sample
+                image = self.scheduler.step(model_output, t, image, eta=eta, generator=generator, **extra).prev_sample
         finally:
             fwd.close()
         return _to_output(self, image, output_type, return_dict)

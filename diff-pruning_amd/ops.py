@@ -2216,6 +2216,121 @@ def unipc_step(e, x_pred, coef, pc=0, pp=1, predict_x0=True, x_last=None, hist=(
     return out, x_c, m_new
 
 
+THRESHOLD_LDS_MAX = 16384            # DP_THRESHOLD_LDS_MAX (include/dp_hip.h): the longest row the one-workgroup-per-image route keeps in LDS
+X0_STEP_MAX_BLOCKS = 4096            # DP_X0_STEP_MAX_BLOCKS: 256 lanes each, strided over rows and images beyond
+X0_PRED_EPSILON, X0_PRED_SAMPLE, X0_PRED_V = 0, 1, 2
+X0_PRED = {'epsilon': X0_PRED_EPSILON, 'sample': X0_PRED_SAMPLE, 'v_prediction': X0_PRED_V}
+X0_TREAT_NONE, X0_TREAT_CLIP, X0_TREAT_THRESHOLD = 0, 1, 2
+X0_MODE_DDIM, X0_MODE_DDPM, X0_MODE_CONVERT = 0, 1, 2
+X0_ROUTE_LDS, X0_ROUTE_MULTI = 1, 2
+X0_COEF = ('sa', 'sb', 'range', 'c0', 'c1', 'cz')
+X0_HOST_COEF = ('ratio', 'max_value')        # read by the host only: the quantile of a thresholded x0_step without `stats`
+
+
+def quantile_rank(ratio, n):
+    """(lo, hi, w) of torch.quantile's linear interpolation over n sorted values: r = fp32(ratio) * fp32(n - 1) rounded in fp32,
+    lo = floor r, hi = ceil r, w = r - lo in fp32."""
+    if not 0.0 <= float(ratio) <= 1.0:
+        raise ValueError('quantile() q values must be in the range [0, 1]')
+    r = torch.tensor(float(ratio), dtype=_f32) * (int(n) - 1)
+    lo = torch.floor(r)
+    return int(lo), int(torch.ceil(r)), float(r - lo)
+
+
+def _rows(t):
+    return t.shape[0], (t.numel() // t.shape[0] if t.shape[0] else 0)
+
+
+def _x0_route(route, n):
+    if route is None:
+        return X0_ROUTE_LDS if n <= THRESHOLD_LDS_MAX else X0_ROUTE_MULTI
+    assert route in (X0_ROUTE_LDS, X0_ROUTE_MULTI), route
+    if route == X0_ROUTE_LDS and n > THRESHOLD_LDS_MAX:
+        raise ValueError('x0_abs_quantile: a row of %d elements does not fit the LDS route (at most %d)' % (n, THRESHOLD_LDS_MAX))
+    return route
+
+
+def x0_abs_quantile(x, m, pred, sa, sb, ratio, max_value, route=None):
+    """stats[B, 4] = (v_lo, v_hi, quantile, s) per image of the |x0| that model output `m` and sample `x` ([B, ...] fp32) form
+    (dp_x0_abs_quantile, csrc/threshold.hip): the two order statistics torch.quantile(|x0|.reshape(B, -1), ratio, dim=1) interpolates
+    between, selected exactly, its value bit for bit, and s = clamp(quantile, min=1, max=max_value) -- the reference's
+    _threshold_sample up to its clamp.  `pred`: X0_PRED_EPSILON | X0_PRED_SAMPLE (x may be None) | X0_PRED_V; sa, sb: the host's fp32
+    alpha_prod_t ** 0.5 and beta_prod_t ** 0.5.  `route`: X0_ROUTE_LDS (rows up to THRESHOLD_LDS_MAX), X0_ROUTE_MULTI, None: by
+    the row length.  Stays on the device."""
+    B, n = _rows(m)
+    assert m.dtype == _f32 and m.is_contiguous() and n >= 1
+    assert pred in (X0_PRED_EPSILON, X0_PRED_SAMPLE, X0_PRED_V)
+    if pred == X0_PRED_SAMPLE:
+        x = None
+    else:
+        assert x is not None and x.dtype == _f32 and x.is_contiguous() and tuple(x.shape) == tuple(m.shape)
+    route = _x0_route(route, n)
+    lo, hi, w = quantile_rank(ratio, n)
+    stats = torch.empty((B, 4), dtype=_f32, device=m.device)
+    ws = None
+    if route == X0_ROUTE_MULTI:
+        ws = torch.empty(max(int(_lib().dp_x0_abs_quantile_workspace(B, n)), 1), dtype=torch.uint8, device=m.device)
+    L.check(_lib().dp_x0_abs_quantile(_p(x), _p(m), B, n, int(pred), float(sa), float(sb), lo, hi, w, float(max_value), route, _p(ws),
+                                      _p(stats), _stream()), 'dp_x0_abs_quantile')
+    return stats
+
+
+def x0_step(x, m, mode, pred, treat, coef, stats=None, z=None, out=None, x0_out=None, reclip=False, route=None):
+    """One DDIM / DDPM scheduler step for an epsilon, sample or v-prediction model over [B, ...] fp32 data, one pass (dp_x0_step,
+    csrc/threshold.hip).  `coef`: the host's fp32 scalars by name (X0_COEF; one a mode does not read may be left out):
+    x0, eps = (x - sb m) / sa, m | m, (x - sa m) / sb | sa x - sb m, sa m + sb x;
+    `treat` X0_TREAT_NONE | X0_TREAT_CLIP: x0 = clamp(x0, -range, range) | X0_TREAT_THRESHOLD: x0 = clamp(x0, -s, s) / s with the
+    image's s; `reclip`: eps = (x - sa x0) / sb from the treated x0;
+    `mode` X0_MODE_DDIM: out = c0 x0 + c1 eps [+ cz z] | X0_MODE_DDPM: out = c0 x0 + c1 x [+ cz z] | X0_MODE_CONVERT: out = the
+    treated x0 (no z, no x0_out; x may be None for a sample model).  `x0_out` (optional) takes the treated x0.
+    A thresholded step takes s from `stats` (x0_abs_quantile's table) when given.  Without it, coef['ratio'] and coef['max_value']
+    say which quantile: a row up to THRESHOLD_LDS_MAX is ONE launch (dp_x0_threshold_step: the workgroup that selected an image's s
+    applies it), a longer one -- or `route` X0_ROUTE_MULTI -- the quantile's launches and then the step; the same bits either way.
+    `out` may be `x`; no other buffer may be shared.  Returns (out, x0_out, stats)."""
+    B, n = _rows(m)
+    assert mode in (X0_MODE_DDIM, X0_MODE_DDPM, X0_MODE_CONVERT) and treat in (X0_TREAT_NONE, X0_TREAT_CLIP, X0_TREAT_THRESHOLD)
+    assert pred in (X0_PRED_EPSILON, X0_PRED_SAMPLE, X0_PRED_V)
+    assert m.dtype == _f32 and m.is_contiguous() and n >= 1
+    if mode == X0_MODE_CONVERT and pred == X0_PRED_SAMPLE:
+        x = None
+    else:
+        assert x is not None and x.dtype == _f32 and x.is_contiguous() and tuple(x.shape) == tuple(m.shape)
+    if mode == X0_MODE_CONVERT:
+        assert z is None and x0_out is None, 'x0_step: CONVERT writes the treated x0 alone'
+    assert z is None or (z.dtype == _f32 and z.is_contiguous() and z.numel() == m.numel())
+    if out is None:
+        out = torch.empty_like(m)
+    outs = [o for o in (out, x0_out) if o is not None]
+    for o in outs:
+        assert o.dtype == _f32 and o.is_contiguous() and o.numel() == m.numel()
+    unknown = set(coef) - set(X0_COEF) - set(X0_HOST_COEF)
+    assert not unknown, unknown
+    c = L.X0Coef(**{k: float(v) for k, v in coef.items() if k in X0_COEF})
+    args = (int(mode), int(pred))
+    if treat == X0_TREAT_THRESHOLD and stats is None:
+        ratio, max_value = float(coef['ratio']), float(coef['max_value'])
+        if _x0_route(route, n) == X0_ROUTE_LDS:
+            lo, hi, w = quantile_rank(ratio, n)
+            stats = torch.empty((B, 4), dtype=_f32, device=m.device)
+            L.check(_lib().dp_x0_threshold_step(_p(x), _p(m), _p(z), *args, 1 if reclip else 0, C.byref(c), lo, hi, w, max_value,
+                                                _p(out), _p(x0_out), _p(stats), B, n, _stream()), 'dp_x0_threshold_step')
+            return out, x0_out, stats
+        stats = x0_abs_quantile(x, m, pred, c.sa, c.sb, ratio, max_value, route=X0_ROUTE_MULTI)
+    if treat == X0_TREAT_THRESHOLD:
+        assert stats.dtype == _f32 and stats.is_contiguous() and tuple(stats.shape) == (B, 4)
+    L.check(_lib().dp_x0_step(_p(x), _p(m), _p(z), _p(stats) if treat == X0_TREAT_THRESHOLD else None, *args, int(treat),
+                              1 if reclip else 0, C.byref(c), _p(out), _p(x0_out), B, n, _stream()), 'dp_x0_step')
+    return out, x0_out, stats
+
+
+def dynamic_threshold(sample, ratio=0.995, max_value=1.0, out=None):
+    """The reference's `_threshold_sample` (scheduling_ddpm.py:278-310) for a caller's own [B, C, H, W] fp32 tensor: per image
+    s = clamp(quantile(|sample|, ratio), min=1, max=max_value), sample = clamp(sample, -s, s) / s -- one launch for a row up to
+    THRESHOLD_LDS_MAX.  With the default max_value = 1.0 every s is 1 and this is a clip to [-1, 1]."""
+    return x0_step(None, sample, X0_MODE_CONVERT, X0_PRED_SAMPLE, X0_TREAT_THRESHOLD, dict(sa=1.0, sb=0.0, ratio=ratio, max_value=max_value),
+                   out=out)[0]
+
+
 VAE_MAX_BLOCKS = 4096                # DP_VAE_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, grid-stride beyond
 POSTERIOR_OUTPUTS = ('logvar', 'std', 'var', 'z', 'kl')
 

@@ -622,6 +622,58 @@ int dp_unipc_step(const float* e, const float* x_pred, const float* x_last, cons
                   int pc, int pp, int predict_x0, const dp_unipc_coef* coef, float* m_new, float* x_c, float* x_next, long long n,
                   void* stream);
 
+/* x0 forming, dynamic thresholding and the DDPM / DDIM update for epsilon, sample and v-prediction models (csrc/threshold.hip;
+ * diffusers/schedulers/scheduling_ddpm.py:278-310, :355-401, scheduling_ddim.py:205-237, :334-385) over B images of n fp32 elements.
+ * sa, sb: the host's fp32 alpha_prod_t ** 0.5 and beta_prod_t ** 0.5.
+ *   model DP_X0_PRED_EPSILON: x0 = (x - sb m) / sa, eps = m;  _SAMPLE: x0 = m, eps = (x - sa x0) / sb from the untreated x0;
+ *   _V: x0 = sa x - sb m, eps = sa m + sb x.  Every operation rounded on its own, true divisions.
+ *
+ * dp_x0_abs_quantile: stats[b] = (v_lo, v_hi, quantile, s) of image b: v_lo, v_hi the order statistics lo and hi (0-based,
+ * hi = lo or lo + 1 < n) of the row's |x0|, exact (-0 counts as +0, a NaN as the largest key); quantile = fma(w, v_hi - v_lo, v_lo)
+ * for w < 0.5, fma(w - 1, v_hi - v_lo, v_hi) otherwise (torch.quantile's lerp; lo, hi, w: the rank the host formed as torch does),
+ * NaN for a row that holds a NaN; s = clamp(quantile, 1, max_value) as torch.clamp (a NaN stays, max_value < 1 gives max_value).
+ * route DP_X0_ROUTE_LDS: one workgroup per image, the row in LDS, n <= DP_THRESHOLD_LDS_MAX; _MULTI: any n < 2^31, per-image digit
+ * histograms in ws (dp_x0_abs_quantile_workspace(B, n) bytes), x0 recomputed in each of the five passes over x and m; _AUTO: by n.
+ * x may be NULL for a sample model.  Nothing is read back; two calls give the same bits.
+ *
+ * dp_x0_step: one pass.  x0 treated as DP_X0_TREAT_NONE | _CLIP (clamp(x0, -range, range)) | _THRESHOLD (clamp(x0, -s, s) / s with
+ * s = stats[b][3]); reclip: eps = (x - sa x0) / sb from the treated x0;
+ *   DP_X0_MODE_DDIM: prev = c0 x0 + c1 eps [+ cz z];  _DDPM: prev = (c0 x0 + c1 x) + (cz z, or 0 without z);
+ *   _CONVERT: prev = the treated x0 (z and x0_out must be NULL; x may be NULL for a sample model).
+ * x0_out (optional) takes the treated x0.  prev may be x itself; any other overlap between an output (or stats) and another buffer is
+ * hipErrorInvalidValue.  16-byte accesses between a scalar head and tail when n % 4 == 0 and all pointers in use share one alignment
+ * modulo 16, 4-byte accesses otherwise; at most DP_X0_STEP_MAX_BLOCKS blocks of 256 lanes, strided over rows and images beyond.
+ *
+ * dp_x0_threshold_step: the LDS route of the quantile with the thresholded step applied by the same workgroup, ONE launch for
+ * n <= DP_THRESHOLD_LDS_MAX; writes prev, x0_out (optional) and stats; the bits of dp_x0_abs_quantile followed by dp_x0_step. */
+#define DP_THRESHOLD_LDS_MAX 16384
+#define DP_X0_STEP_MAX_BLOCKS 4096
+#define DP_X0_PRED_EPSILON 0
+#define DP_X0_PRED_SAMPLE 1
+#define DP_X0_PRED_V 2
+#define DP_X0_TREAT_NONE 0
+#define DP_X0_TREAT_CLIP 1
+#define DP_X0_TREAT_THRESHOLD 2
+#define DP_X0_MODE_DDIM 0
+#define DP_X0_MODE_DDPM 1
+#define DP_X0_MODE_CONVERT 2
+#define DP_X0_ROUTE_AUTO 0
+#define DP_X0_ROUTE_LDS 1
+#define DP_X0_ROUTE_MULTI 2
+typedef struct dp_x0_coef {
+    float sa, sb;                       /* forming x0 and eps */
+    float range;                        /* DP_X0_TREAT_CLIP */
+    float c0, c1, cz;                   /* the update: factors of x0, of eps (DDIM) or x (DDPM), of z */
+} dp_x0_coef;
+long long dp_x0_abs_quantile_workspace(long long B, long long n);
+int dp_x0_abs_quantile(const float* x, const float* m, long long B, long long n, int pred, float sa, float sb, long long lo,
+                       long long hi, float w, float max_value, int route, void* ws, float* stats, void* stream);
+int dp_x0_step(const float* x, const float* m, const float* z, const float* stats, int mode, int pred, int treat, int reclip,
+               const dp_x0_coef* coef, float* prev, float* x0_out, long long B, long long n, void* stream);
+int dp_x0_threshold_step(const float* x, const float* m, const float* z, int mode, int pred, int reclip, const dp_x0_coef* coef,
+                         long long lo, long long hi, float w, float max_value, float* prev, float* x0_out, float* stats,
+                         long long B, long long n, void* stream);
+
 /* ---- LDM (CompVis) transformer-block glue on channel-major tokens x[n][c][t]  (ldm_exp/ldm/modules/attention.py) ---- */
 /* LayerNorm over the C channels of every token (attention.py:200-212 norm1/2/3); stats[(n*T+t)*2+{0,1}] = {mean, rstd}. */
 int dp_layernorm_fwd(const float* x, long long x_img_stride, const float* gamma, const float* beta, int N, int C, int T,
