@@ -16,7 +16,7 @@
 // the reference's order (diffusion.DPMSolverMultistepScheduler) -- the way dp_denoise_step takes its coefficients.
 //
 // Memory bound: 4 (order + 1) B read and 8 B written per element, 16-byte accesses, nothing else.  Plain vector loads and stores.
-#include "dp_common.h"
+#include "dp_headtail.h"
 
 // The launch macro of this file: the body of the library's own (dp_common.h) under a name of its own, so that the launch sites of
 // this file are tabled by this file's test module (tests/test_dpm_solver_gpu.py), as stage.hip, evalmetrics.hip and prune_global.hip do.
@@ -53,52 +53,32 @@ __device__ __forceinline__ float dpm_solver_one(float x, float e, float m1, floa
     return v;
 }
 
-// Elements [0, head) and [head + 4 * n4, n) take 4-byte accesses, the n4 = (n - head) / 4 groups between them 16-byte ones.  The
-// launcher chooses head so that every pointer + head is 16-byte aligned, or head = n when the pointers do not share one alignment.
-// `next` may be `x` itself and `m0_out` may be `m1` or `m2` itself (no __restrict__ on those): a lane reads every input of its
-// elements before it writes any of them, and no other lane touches them.  e aliases nothing.
+// The head / body / tail loop of dp_headtail.h.  `next` may be `x` itself and `m0_out` may be `m1` or `m2` itself (no __restrict__ on
+// those): a lane reads every input of its elements before it writes any of them, and no other lane touches them.  e aliases nothing.
 template <int ORDER, bool DATA>
 __global__ __launch_bounds__(256) void dpm_solver_step_kernel(const float* x, const float* __restrict__ e, const float* m1, const float* m2,
                                                               dp_dpm_solver_coef c, float* next, float* m0_out, long long n, long long head) {
-    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long stride = (long long)gridDim.x * 256;
-    const long long n4 = (n - head) / 4;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long i = tid; i < n4; i += stride) {
-        const long long at = head + 4 * i;
-        const float4 xv = *reinterpret_cast<const float4*>(x + at);
-        const float4 ev = *reinterpret_cast<const float4*>(e + at);
-        const float4 av = ORDER >= 2 ? *reinterpret_cast<const float4*>(m1 + at) : zero;
-        const float4 bv = ORDER >= 3 ? *reinterpret_cast<const float4*>(m2 + at) : zero;
-        float4 ov, mv;
-        ov.x = dpm_solver_one<ORDER, DATA>(xv.x, ev.x, av.x, bv.x, c, mv.x);
-        ov.y = dpm_solver_one<ORDER, DATA>(xv.y, ev.y, av.y, bv.y, c, mv.y);
-        ov.z = dpm_solver_one<ORDER, DATA>(xv.z, ev.z, av.z, bv.z, c, mv.z);
-        ov.w = dpm_solver_one<ORDER, DATA>(xv.w, ev.w, av.w, bv.w, c, mv.w);
-        *reinterpret_cast<float4*>(next + at) = ov;                  // after every load of this lane's elements
-        *reinterpret_cast<float4*>(m0_out + at) = mv;
-    }
-    const long long ns = n - 4 * n4;                  // the scalar head and tail (everything when head == n)
-    for (long long j = tid; j < ns; j += stride) {
-        const long long i = j < head ? j : 4 * n4 + j;
-        const float xs = x[i], es = e[i];
-        const float as = ORDER >= 2 ? m1[i] : 0.f;
-        const float bs = ORDER >= 3 ? m2[i] : 0.f;
-        float m;
-        const float v = dpm_solver_one<ORDER, DATA>(xs, es, as, bs, c, m);
-        next[i] = v;
-        m0_out[i] = m;
-    }
-}
-
-// [a, a + 4 n) and [b, b + 4 n) share a byte without being the same buffer
-static inline bool ds_partial_overlap(const void* a, const void* b, long long n) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b, len = 4ull * (unsigned long long)n;
-    return a0 != b0 && a0 < b0 + len && b0 < a0 + len;
-}
-
-static inline bool ds_overlap(const void* a, const void* b, long long n) {
-    return a == b || ds_partial_overlap(a, b, n);
+    dp_ht_for(
+        n, head, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256,
+        [&](long long at) {
+            const float4 xv = dp_ld4(x, at, true), ev = dp_ld4(e, at, true);
+            const float4 av = dp_ld4(m1, at, ORDER >= 2), bv = dp_ld4(m2, at, ORDER >= 3);
+            float4 ov, mv;
+            ov.x = dpm_solver_one<ORDER, DATA>(xv.x, ev.x, av.x, bv.x, c, mv.x);
+            ov.y = dpm_solver_one<ORDER, DATA>(xv.y, ev.y, av.y, bv.y, c, mv.y);
+            ov.z = dpm_solver_one<ORDER, DATA>(xv.z, ev.z, av.z, bv.z, c, mv.z);
+            ov.w = dpm_solver_one<ORDER, DATA>(xv.w, ev.w, av.w, bv.w, c, mv.w);
+            dp_st4(next, at, ov);                                    // after every load of this lane's elements
+            dp_st4(m0_out, at, mv);
+        },
+        [&](long long i) {
+            const float xs = x[i], es = e[i];
+            const float as = dp_ld1(m1, i, ORDER >= 2), bs = dp_ld1(m2, i, ORDER >= 3);
+            float m;
+            const float v = dpm_solver_one<ORDER, DATA>(xs, es, as, bs, c, m);
+            next[i] = v;
+            m0_out[i] = m;
+        });
 }
 
 extern "C" int dp_dpm_solver_step(const float* x, const float* e, const float* m1, const float* m2, int order, int data_pred,
@@ -109,21 +89,15 @@ extern "C" int dp_dpm_solver_step(const float* x, const float* e, const float* m
     if (order < 2) m1 = nullptr;
     if ((order >= 2 && !m1) || (order >= 3 && !m2)) return (int)hipErrorInvalidValue;
     // the aliases the kernel is written for: x_next == x, m0_out == m1, m0_out == m2.  Everything else is disjoint.
-    if (ds_partial_overlap(x_next, x, n) || ds_overlap(x_next, e, n) || ds_overlap(x_next, m0_out, n)) return (int)hipErrorInvalidValue;
-    if (ds_overlap(m0_out, x, n) || ds_overlap(m0_out, e, n)) return (int)hipErrorInvalidValue;
-    if (m1 && (ds_overlap(x_next, m1, n) || ds_partial_overlap(m0_out, m1, n))) return (int)hipErrorInvalidValue;
-    if (m2 && (ds_overlap(x_next, m2, n) || ds_partial_overlap(m0_out, m2, n))) return (int)hipErrorInvalidValue;
-    // one alignment for every pointer -> a scalar head of 0 .. 3 elements brings all of them to 16 bytes; otherwise all scalar
-    const uintptr_t a = (uintptr_t)x & 15;
-    bool same = (a & 3) == 0 && ((uintptr_t)e & 15) == a && ((uintptr_t)x_next & 15) == a && ((uintptr_t)m0_out & 15) == a;
-    if (m1) same = same && ((uintptr_t)m1 & 15) == a;
-    if (m2) same = same && ((uintptr_t)m2 & 15) == a;
-    long long head = same ? (long long)(((16 - a) & 15) / 4) : n;
-    if (head > n) head = n;
-    const long long n4 = (n - head) / 4;
-    const long long work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
-    const long long nb = (work + 255) / 256;
-    const unsigned grid = (unsigned)(nb > DP_DPM_SOLVER_MAX_BLOCKS ? DP_DPM_SOLVER_MAX_BLOCKS : nb < 1 ? 1 : nb);
+    const unsigned long long len = 4ull * (unsigned long long)n;
+    const auto hit = [len](const void* a, const void* b) { return dp_bytes_overlap(a, len, b, len); };
+    if ((x_next != x && hit(x_next, x)) || hit(x_next, e) || hit(x_next, m0_out)) return (int)hipErrorInvalidValue;
+    if (hit(m0_out, x) || hit(m0_out, e)) return (int)hipErrorInvalidValue;
+    if (hit(x_next, m1) || (m0_out != m1 && hit(m0_out, m1))) return (int)hipErrorInvalidValue;
+    if (hit(x_next, m2) || (m0_out != m2 && hit(m0_out, m2))) return (int)hipErrorInvalidValue;
+    const void* ptrs[6] = {x, e, x_next, m0_out, m1, m2};
+    const long long head = dp_ht_head(n, ptrs, 6);
+    const unsigned grid = dp_ht_blocks(n, head, DP_DPM_SOLVER_MAX_BLOCKS);
     const dp_dpm_solver_coef c = *coef;
     const hipStream_t st = (hipStream_t)stream;
     // one site per instantiation: the launch ring keeps the stringised kernel expression of the site that launched

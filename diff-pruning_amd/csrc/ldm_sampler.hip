@@ -11,7 +11,7 @@
 // fuse a * b + c into one v_fma_f32), the divisions are true IEEE divisions, and the five per-step scalars arrive from the host
 // (ldm_sampler.sampling_tables), which forms them as the reference's torch.full((b, 1, 1, 1), table[index]) and the fp32 ops
 // that follow it do.  dp_cfg_combine / dp_ddim_step (elementwise.hip) share no device code with this file and are unchanged.
-#include "dp_common.h"
+#include "dp_headtail.h"
 
 struct CfgDenoiseCoef {
     float scale, s1m, sqrt_a_t, sqrt_a_prev, c_dir, sigma, temperature;
@@ -79,10 +79,9 @@ __device__ __forceinline__ float cfg_denoise_one(float x, float eu, float ec, fl
     return v;
 }
 
-// Elements [0, head) and [head + 4 * n4, n) take 4-byte accesses, the n4 = (n - head) / 4 groups between them 16-byte ones.  The
-// launcher chooses head so that every pointer + head is 16-byte aligned, or head = n when the pointers do not share one alignment
-// (e_c = e_u + n with n % 4 != 0, for one).  `next` may be `x` itself (no __restrict__ on the two): an element is read and written
-// by the same lane, in that order.  x0_out and eg_out alias nothing.  A history pointer ORDER does not read is never touched.
+// The head / body / tail loop of dp_headtail.h (all scalar with e_c = e_u + n and n % 4 != 0, for one).  `next` may be `x` itself
+// (no __restrict__ on the two): an element is read and written by the same lane, in that order.  x0_out and eg_out alias nothing.
+// A history pointer ORDER does not read is never touched.
 template <int ORDER, bool GUIDED>
 __global__ __launch_bounds__(256) void cfg_denoise_step_kernel(const float* x, const float* __restrict__ e_u,
                                                                const float* __restrict__ e_c, const float* __restrict__ h1,
@@ -91,48 +90,29 @@ __global__ __launch_bounds__(256) void cfg_denoise_step_kernel(const float* x, c
                                                                float* __restrict__ x0_out, float* __restrict__ eg_out, long long n,
                                                                long long head) {
     constexpr bool H1 = ORDER >= 1, H2 = ORDER == 2 || ORDER == 3, H3 = ORDER == 3;
-    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long stride = (long long)gridDim.x * 256;
-    const long long n4 = (n - head) / 4;
     const bool has_z = z != nullptr;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4* x4 = reinterpret_cast<const float4*>(x + head);
-    const float4* u4 = reinterpret_cast<const float4*>(e_u + head);
-    const float4* c4 = reinterpret_cast<const float4*>(GUIDED ? e_c + head : nullptr);
-    const float4* a4 = reinterpret_cast<const float4*>(H1 ? h1 + head : nullptr);
-    const float4* b4 = reinterpret_cast<const float4*>(H2 ? h2 + head : nullptr);
-    const float4* d4 = reinterpret_cast<const float4*>(H3 ? h3 + head : nullptr);
-    const float4* z4 = reinterpret_cast<const float4*>(has_z ? z + head : nullptr);
-    float4* o4 = reinterpret_cast<float4*>(next + head);
-    float4* p4 = reinterpret_cast<float4*>(x0_out ? x0_out + head : nullptr);
-    float4* g4 = reinterpret_cast<float4*>(eg_out ? eg_out + head : nullptr);
-    for (long long i = tid; i < n4; i += stride) {
-        const float4 xv = x4[i];
-        const float4 uv = u4[i];
-        const float4 cv = GUIDED ? c4[i] : zero;
-        const float4 av = H1 ? a4[i] : zero;
-        const float4 bv = H2 ? b4[i] : zero;
-        const float4 dv = H3 ? d4[i] : zero;
-        const float4 zv = has_z ? z4[i] : zero;
-        float4 ov, pv, gv;
-        ov.x = cfg_denoise_one<ORDER, GUIDED>(xv.x, uv.x, cv.x, av.x, bv.x, dv.x, zv.x, has_z, c, pv.x, gv.x);
-        ov.y = cfg_denoise_one<ORDER, GUIDED>(xv.y, uv.y, cv.y, av.y, bv.y, dv.y, zv.y, has_z, c, pv.y, gv.y);
-        ov.z = cfg_denoise_one<ORDER, GUIDED>(xv.z, uv.z, cv.z, av.z, bv.z, dv.z, zv.z, has_z, c, pv.z, gv.z);
-        ov.w = cfg_denoise_one<ORDER, GUIDED>(xv.w, uv.w, cv.w, av.w, bv.w, dv.w, zv.w, has_z, c, pv.w, gv.w);
-        o4[i] = ov;
-        if (x0_out) p4[i] = pv;
-        if (eg_out) g4[i] = gv;
-    }
-    const long long ns = n - 4 * n4;                  // the scalar head and tail (everything when head == n)
-    for (long long j = tid; j < ns; j += stride) {
-        const long long i = j < head ? j : 4 * n4 + j;
-        float p, g;
-        const float v = cfg_denoise_one<ORDER, GUIDED>(x[i], e_u[i], GUIDED ? e_c[i] : 0.f, H1 ? h1[i] : 0.f, H2 ? h2[i] : 0.f,
-                                                       H3 ? h3[i] : 0.f, has_z ? z[i] : 0.f, has_z, c, p, g);
-        next[i] = v;
-        if (x0_out) x0_out[i] = p;
-        if (eg_out) eg_out[i] = g;
-    }
+    dp_ht_for(
+        n, head, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256,
+        [&](long long at) {
+            const float4 xv = dp_ld4(x, at, true), uv = dp_ld4(e_u, at, true), cv = dp_ld4(e_c, at, GUIDED);
+            const float4 av = dp_ld4(h1, at, H1), bv = dp_ld4(h2, at, H2), dv = dp_ld4(h3, at, H3), zv = dp_ld4(z, at, has_z);
+            float4 ov, pv, gv;
+            ov.x = cfg_denoise_one<ORDER, GUIDED>(xv.x, uv.x, cv.x, av.x, bv.x, dv.x, zv.x, has_z, c, pv.x, gv.x);
+            ov.y = cfg_denoise_one<ORDER, GUIDED>(xv.y, uv.y, cv.y, av.y, bv.y, dv.y, zv.y, has_z, c, pv.y, gv.y);
+            ov.z = cfg_denoise_one<ORDER, GUIDED>(xv.z, uv.z, cv.z, av.z, bv.z, dv.z, zv.z, has_z, c, pv.z, gv.z);
+            ov.w = cfg_denoise_one<ORDER, GUIDED>(xv.w, uv.w, cv.w, av.w, bv.w, dv.w, zv.w, has_z, c, pv.w, gv.w);
+            dp_st4(next, at, ov);
+            if (x0_out) dp_st4(x0_out, at, pv);
+            if (eg_out) dp_st4(eg_out, at, gv);
+        },
+        [&](long long i) {
+            float p, g;
+            const float v = cfg_denoise_one<ORDER, GUIDED>(x[i], e_u[i], dp_ld1(e_c, i, GUIDED), dp_ld1(h1, i, H1), dp_ld1(h2, i, H2),
+                                                           dp_ld1(h3, i, H3), dp_ld1(z, i, has_z), has_z, c, p, g);
+            next[i] = v;
+            if (x0_out) x0_out[i] = p;
+            if (eg_out) eg_out[i] = g;
+        });
 }
 
 // literal template arguments, so that the name DP_LAUNCH records says which instantiation ran
@@ -154,23 +134,10 @@ extern "C" int dp_cfg_denoise_step(const float* x, const float* e_u, const float
     if (!x || !e_u || !next || order < 0 || order > 4) return (int)hipErrorInvalidValue;
     const bool need1 = order >= 1, need2 = order == 2 || order == 3, need3 = order == 3;
     if ((need1 && !h1) || (need2 && !h2) || (need3 && !h3)) return (int)hipErrorInvalidValue;
-    // one alignment for every pointer that is read or written -> a scalar head of 0 .. 3 elements brings all of them to 16 bytes;
-    // otherwise all scalar
-    const uintptr_t a = (uintptr_t)x & 15;
-    bool same = ((uintptr_t)e_u & 15) == a && ((uintptr_t)next & 15) == a && (a & 3) == 0;
-    if (e_c) same = same && ((uintptr_t)e_c & 15) == a;
-    if (need1) same = same && ((uintptr_t)h1 & 15) == a;
-    if (need2) same = same && ((uintptr_t)h2 & 15) == a;
-    if (need3) same = same && ((uintptr_t)h3 & 15) == a;
-    if (z) same = same && ((uintptr_t)z & 15) == a;
-    if (x0_out) same = same && ((uintptr_t)x0_out & 15) == a;
-    if (eg_out) same = same && ((uintptr_t)eg_out & 15) == a;
-    long long head = same ? (long long)(((16 - a) & 15) / 4) : n;
-    if (head > n) head = n;
-    const long long n4 = (n - head) / 4;
-    const long long work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
-    const long long nb = (work + 255) / 256;
-    const unsigned grid = (unsigned)(nb > DP_DENOISE_MAX_BLOCKS ? DP_DENOISE_MAX_BLOCKS : nb < 1 ? 1 : nb);
+    // only the pointers that are read or written count: a history pointer the order does not read is left out
+    const void* ptrs[10] = {x, e_u, next, e_c, need1 ? h1 : nullptr, need2 ? h2 : nullptr, need3 ? h3 : nullptr, z, x0_out, eg_out};
+    const long long head = dp_ht_head(n, ptrs, 10);
+    const unsigned grid = dp_ht_blocks(n, head, DP_DENOISE_MAX_BLOCKS);
     const CfgDenoiseCoef c{scale, s1m, sqrt_a_t, sqrt_a_prev, c_dir, sigma, temperature};
     const hipStream_t s = (hipStream_t)stream;
     switch (order) {

@@ -12,6 +12,7 @@
 // them with 0-d fp32 torch ops in the reference's order (ddpm_exp_sampler.py) -- the way dp_ddpm_step takes its coefficients.
 // dp_ddim_step / dp_ddpm_step (elementwise.hip) share no device code with this file and are unchanged.
 #include "dp_common.h"
+#include "dp_headtail_plan.h"
 
 struct DenoiseCoef {
     float p0, p1, p2, p3, p4, p5;
@@ -48,10 +49,10 @@ __device__ __forceinline__ float denoise_one(float x, float e, float z, bool has
     }
 }
 
-// Elements [0, head) and [head + 4 * n4, n) take 4-byte accesses, the n4 = (n - head) / 4 groups between them 16-byte ones.  The
-// launcher chooses head so that x + head (and every other pointer + head) is 16-byte aligned, or head = n when the pointers do
-// not share one alignment.  `next` may be `x` itself (no __restrict__ on the two): an element is read and written by the same
-// lane, in that order.  x0_out aliases nothing.
+// The head / body / tail loop of dp_headtail.h (dp_ht_for), written out: this kernel pre-offsets its bases (x + head) where dp_ht_for's
+// callers index x + at, and the dp_ht_for form of it timed slower than this one beyond the run-to-run spread in 2 of 6 comparisons
+// (profiles/headtail_refactor.md), so the loop stays as it was.  `next` may be `x` itself (no __restrict__ on the two): an element is
+// read and written by the same lane, in that order.  x0_out aliases nothing.
 template <int MODE>
 __global__ __launch_bounds__(256) void denoise_step_kernel(const float* x, const float* __restrict__ e, const float* __restrict__ z,
                                                            DenoiseCoef c, float* next, float* __restrict__ x0_out, long long n,
@@ -91,17 +92,9 @@ extern "C" int dp_denoise_step(const float* x, const float* eps, const float* z,
                                float p4, float p5, float* next, float* x0_out, long long n, void* stream) {
     if (n <= 0) return 0;
     if (!x || !eps || !next || (mode != 0 && mode != 1)) return (int)hipErrorInvalidValue;
-    // one alignment for every pointer -> a scalar head of 0 .. 3 elements brings all of them to 16 bytes; otherwise all scalar
-    const uintptr_t a = (uintptr_t)x & 15;
-    bool same = ((uintptr_t)eps & 15) == a && ((uintptr_t)next & 15) == a && (a & 3) == 0;
-    if (z) same = same && ((uintptr_t)z & 15) == a;
-    if (x0_out) same = same && ((uintptr_t)x0_out & 15) == a;
-    long long head = same ? (long long)(((16 - a) & 15) / 4) : n;
-    if (head > n) head = n;
-    const long long n4 = (n - head) / 4;
-    const long long work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
-    const long long nb = (work + 255) / 256;
-    const unsigned grid = (unsigned)(nb > DP_DENOISE_MAX_BLOCKS ? DP_DENOISE_MAX_BLOCKS : nb < 1 ? 1 : nb);
+    const void* ptrs[5] = {x, eps, next, z, x0_out};
+    const long long head = dp_ht_head(n, ptrs, 5);
+    const unsigned grid = dp_ht_blocks(n, head, DP_DENOISE_MAX_BLOCKS);
     const DenoiseCoef c{p0, p1, p2, p3, p4, p5};
     if (mode == 0)
         DP_LAUNCH(denoise_step_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, eps, z, c, next, x0_out, n, head);

@@ -21,7 +21,7 @@
 // from the host.  The ONE contraction is the explicit fmaf of the quantile's lerp, as torch's lerp has it.  The counters of the select are
 // integers: the order in which they are accumulated does not change them, and no floating-point value depends on scheduling.
 // Plain vector loads and stores, 64-bit element indices.
-#include "dp_common.h"
+#include "dp_headtail.h"
 
 // The launch macro of this file: the body of the library's own (dp_common.h) under a name of its own, so that the launch sites of
 // this file are tabled by this file's test module (tests/test_threshold_gpu.py), as dpm_solver.hip and unipc.hip do.
@@ -148,35 +148,70 @@ __device__ __forceinline__ void th_pick(const unsigned* hist, unsigned k, unsign
     count = __shfl(c, src, 64);
 }
 
-// f(i, x0) for the elements i of one row that the strided lanes (tid, stride) own.  Elements [0, head) and [head + 4 n4, n) take 4-byte
-// loads, the n4 = (n - head) / 4 groups between them 16-byte ones (the launcher chooses head so that the row pointers + head are 16-byte
-// aligned in every row, or head = n).  xr is not read for a `sample` model.
+// f(i, x0) for the elements i of one row that the strided lanes (tid, stride) own, in the head / body / tail loop of dp_headtail.h (the
+// launcher chooses head so that the row pointers + head are 16-byte aligned in every row, or head = n).  xr is not read for a `sample`
+// model.
 template <typename F>
 __device__ __forceinline__ void th_row_x0(const float* __restrict__ xr, const float* __restrict__ mr, long long n, long long head, int pred,
                                           float sa, float sb, long long tid, long long stride, F&& f) {
     const bool need_x = pred != DP_X0_PRED_SAMPLE;
-    const long long n4 = (n - head) / 4;
-    for (long long i = tid; i < n4; i += stride) {
-        const long long at = head + 4 * i;
-        const float4 mv = *reinterpret_cast<const float4*>(mr + at);
-        const float4 xv = need_x ? *reinterpret_cast<const float4*>(xr + at) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float a, b, c, d, e;
-        th_form(pred, xv.x, mv.x, sa, sb, a, e);
-        th_form(pred, xv.y, mv.y, sa, sb, b, e);
-        th_form(pred, xv.z, mv.z, sa, sb, c, e);
-        th_form(pred, xv.w, mv.w, sa, sb, d, e);
-        f(at, a);
-        f(at + 1, b);
-        f(at + 2, c);
-        f(at + 3, d);
-    }
-    const long long ns = n - 4 * n4;
-    for (long long j = tid; j < ns; j += stride) {
-        const long long i = j < head ? j : 4 * n4 + j;
-        float a, e;
-        th_form(pred, need_x ? xr[i] : 0.f, mr[i], sa, sb, a, e);
-        f(i, a);
-    }
+    dp_ht_for(
+        n, head, tid, stride,
+        [&](long long at) {
+            const float4 mv = dp_ld4(mr, at, true), xv = dp_ld4(xr, at, need_x);
+            float a, b, c, d, e;
+            th_form(pred, xv.x, mv.x, sa, sb, a, e);
+            th_form(pred, xv.y, mv.y, sa, sb, b, e);
+            th_form(pred, xv.z, mv.z, sa, sb, c, e);
+            th_form(pred, xv.w, mv.w, sa, sb, d, e);
+            f(at, a);
+            f(at + 1, b);
+            f(at + 2, c);
+            f(at + 3, d);
+        },
+        [&](long long i) {
+            float a, e;
+            th_form(pred, dp_ld1(xr, i, need_x), mr[i], sa, sb, a, e);
+            f(i, a);
+        });
+}
+
+// The treated-x0 update of the elements of one row that the strided lanes (tid, stride) own, in the same loop: form (x0, eps), treat x0
+// with s, update, write pr and (optional) qr.  ROW: x0 is not formed again but read from `row`, where th_row_x0's caller put it (the
+// same bits).  pr may be xr (no __restrict__ on either): a lane reads every input of its elements before it writes any of them, and
+// no other lane touches them.  xr is not read where neither the model nor the update needs x.
+template <bool ROW>
+__device__ __forceinline__ void th_row_update(const ThStep& p, float s, const float* xr, const float* __restrict__ mr, const float* __restrict__ zr,
+                                              const float* row, float* pr, float* __restrict__ qr, long long n, long long head, long long tid,
+                                              long long stride) {
+    const bool need_x = !(p.mode == DP_X0_MODE_CONVERT && p.pred == DP_X0_PRED_SAMPLE);
+    const bool has_z = zr != nullptr;
+    dp_ht_for(
+        n, head, tid, stride,
+        [&](long long at) {
+            const float4 xv = dp_ld4(xr, at, need_x), mv = dp_ld4(mr, at, true), zv = dp_ld4(zr, at, has_z);
+            float4 q, e, o;
+            th_form(p.pred, xv.x, mv.x, p.c.sa, p.c.sb, q.x, e.x);
+            th_form(p.pred, xv.y, mv.y, p.c.sa, p.c.sb, q.y, e.y);
+            th_form(p.pred, xv.z, mv.z, p.c.sa, p.c.sb, q.z, e.z);
+            th_form(p.pred, xv.w, mv.w, p.c.sa, p.c.sb, q.w, e.w);
+            if (ROW) q = dp_ld4(row, at, true);
+            o.x = th_update(p, xv.x, zv.x, has_z, s, q.x, e.x);
+            o.y = th_update(p, xv.y, zv.y, has_z, s, q.y, e.y);
+            o.z = th_update(p, xv.z, zv.z, has_z, s, q.z, e.z);
+            o.w = th_update(p, xv.w, zv.w, has_z, s, q.w, e.w);
+            dp_st4(pr, at, o);                                       // after every load of this lane's elements
+            if (qr) dp_st4(qr, at, q);
+        },
+        [&](long long i) {
+            const float xs = dp_ld1(xr, i, need_x), zs = dp_ld1(zr, i, has_z);
+            float q, e;
+            th_form(p.pred, xs, mr[i], p.c.sa, p.c.sb, q, e);
+            if (ROW) q = row[i];
+            const float o = th_update(p, xs, zs, has_z, s, q, e);
+            pr[i] = o;
+            if (qr) qr[i] = q;
+        });
 }
 
 // ---------------------------------------------------------------------------------------------------- the row in LDS
@@ -253,42 +288,8 @@ __global__ __launch_bounds__(TH_LDS_THREADS) void th_lds_kernel(const float* x, 
     if (!APPLY) return;
     __syncthreads();
     const float s = __uint_as_float(sh[5]);
-    const float* zr = z ? z + b * n : nullptr;
-    float* pr = prev + b * n;
-    float* qr = x0_out ? x0_out + b * n : nullptr;
-    const bool need_x = !(p.mode == DP_X0_MODE_CONVERT && p.pred == DP_X0_PRED_SAMPLE);
-    const bool has_z = zr != nullptr;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const long long n4 = (n - head) / 4;
-    for (long long i = tid; i < n4; i += TH_LDS_THREADS) {
-        const long long at = head + 4 * i;
-        const float4 xv = need_x ? *reinterpret_cast<const float4*>(xr + at) : zero;
-        const float4 mv = *reinterpret_cast<const float4*>(mr + at);
-        const float4 zv = has_z ? *reinterpret_cast<const float4*>(zr + at) : zero;
-        float4 q = *reinterpret_cast<const float4*>(row + at);
-        float4 e, o;
-        float t;
-        th_form(p.pred, xv.x, mv.x, p.c.sa, p.c.sb, t, e.x);
-        th_form(p.pred, xv.y, mv.y, p.c.sa, p.c.sb, t, e.y);
-        th_form(p.pred, xv.z, mv.z, p.c.sa, p.c.sb, t, e.z);
-        th_form(p.pred, xv.w, mv.w, p.c.sa, p.c.sb, t, e.w);
-        o.x = th_update(p, xv.x, zv.x, has_z, s, q.x, e.x);
-        o.y = th_update(p, xv.y, zv.y, has_z, s, q.y, e.y);
-        o.z = th_update(p, xv.z, zv.z, has_z, s, q.z, e.z);
-        o.w = th_update(p, xv.w, zv.w, has_z, s, q.w, e.w);
-        *reinterpret_cast<float4*>(pr + at) = o;                     // after every load of this lane's elements
-        if (qr) *reinterpret_cast<float4*>(qr + at) = q;
-    }
-    const long long ns = n - 4 * n4;
-    for (long long j = tid; j < ns; j += TH_LDS_THREADS) {
-        const long long i = j < head ? j : 4 * n4 + j;
-        const float xs = need_x ? xr[i] : 0.f, zs = has_z ? zr[i] : 0.f;
-        float q = row[i], e, t;
-        th_form(p.pred, xs, mr[i], p.c.sa, p.c.sb, t, e);
-        const float o = th_update(p, xs, zs, has_z, s, q, e);
-        pr[i] = o;
-        if (qr) qr[i] = q;
-    }
+    th_row_update<true>(p, s, xr, mr, z ? z + b * n : nullptr, row, prev + b * n, x0_out ? x0_out + b * n : nullptr, n, head, tid,
+                        TH_LDS_THREADS);
 }
 
 // ---------------------------------------------------------------------------------------------------- the multi-block route
@@ -387,66 +388,17 @@ __global__ __launch_bounds__(256) void th_step_kernel(const float* x, const floa
                                                       const float* __restrict__ stats, ThStep p, float* prev, float* __restrict__ x0_out,
                                                       long long B, long long n, long long head) {
     const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
-    const bool need_x = !(p.mode == DP_X0_MODE_CONVERT && p.pred == DP_X0_PRED_SAMPLE);
-    const bool has_z = z != nullptr;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const long long n4 = (n - head) / 4, ns = n - 4 * n4;
     for (long long b = blockIdx.y; b < B; b += gridDim.y) {
         const float s = p.treat == DP_X0_TREAT_THRESHOLD ? stats[4 * b + 3] : 1.0f;
-        const float* xr = need_x ? x + b * n : nullptr;
-        const float* mr = m + b * n;
-        const float* zr = has_z ? z + b * n : nullptr;
-        float* pr = prev + b * n;
-        float* qr = x0_out ? x0_out + b * n : nullptr;
-        for (long long i = tid; i < n4; i += stride) {
-            const long long at = head + 4 * i;
-            const float4 xv = need_x ? *reinterpret_cast<const float4*>(xr + at) : zero;
-            const float4 mv = *reinterpret_cast<const float4*>(mr + at);
-            const float4 zv = has_z ? *reinterpret_cast<const float4*>(zr + at) : zero;
-            float4 q, e, o;
-            th_form(p.pred, xv.x, mv.x, p.c.sa, p.c.sb, q.x, e.x);
-            th_form(p.pred, xv.y, mv.y, p.c.sa, p.c.sb, q.y, e.y);
-            th_form(p.pred, xv.z, mv.z, p.c.sa, p.c.sb, q.z, e.z);
-            th_form(p.pred, xv.w, mv.w, p.c.sa, p.c.sb, q.w, e.w);
-            o.x = th_update(p, xv.x, zv.x, has_z, s, q.x, e.x);
-            o.y = th_update(p, xv.y, zv.y, has_z, s, q.y, e.y);
-            o.z = th_update(p, xv.z, zv.z, has_z, s, q.z, e.z);
-            o.w = th_update(p, xv.w, zv.w, has_z, s, q.w, e.w);
-            *reinterpret_cast<float4*>(pr + at) = o;                 // after every load of this lane's elements
-            if (qr) *reinterpret_cast<float4*>(qr + at) = q;
-        }
-        for (long long j = tid; j < ns; j += stride) {
-            const long long i = j < head ? j : 4 * n4 + j;
-            const float xs = need_x ? xr[i] : 0.f, zs = has_z ? zr[i] : 0.f;
-            float q, e;
-            th_form(p.pred, xs, mr[i], p.c.sa, p.c.sb, q, e);
-            const float o = th_update(p, xs, zs, has_z, s, q, e);
-            pr[i] = o;
-            if (qr) qr[i] = q;
-        }
+        th_row_update<false>(p, s, x ? x + b * n : nullptr, m + b * n, z ? z + b * n : nullptr, nullptr, prev + b * n,
+                             x0_out ? x0_out + b * n : nullptr, n, head, tid, stride);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------- launchers
-// [a, a + la) and [b, b + lb) bytes share a byte
-static inline bool th_overlap(const void* a, unsigned long long la, const void* b, unsigned long long lb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + lb && b0 < a0 + la;
-}
-
-// The scalar head of every row: 0 .. 3 elements when n % 4 == 0 and every pointer in use shares one alignment modulo 16 (then every
-// row does), else n (all scalar).
-static inline long long th_head(long long n, const void* const* ptrs, int count) {
-    if (n % 4 != 0) return n;
-    uintptr_t a = 16;
-    for (int i = 0; i < count; ++i) {
-        if (!ptrs[i]) continue;
-        const uintptr_t v = (uintptr_t)ptrs[i] & 15;
-        if (a == 16) a = v;
-        if (v != a || (v & 3) != 0) return n;
-    }
-    const long long head = a == 16 ? 0 : (long long)(((16 - a) & 15) / 4);
-    return head > n ? n : head;
+// The scalar head of every row: dp_ht_head's when n % 4 == 0 (then every row has the phase of the first), else n (all scalar).
+static inline long long th_row_head(long long n, const void* const* ptrs, int count) {
+    return n % 4 != 0 ? n : dp_ht_head(n, ptrs, count);
 }
 
 static inline bool th_rank_ok(long long n, long long lo, long long hi, float w) {
@@ -485,11 +437,11 @@ extern "C" int dp_x0_abs_quantile(const float* x, const float* m, long long B, l
     if (pred == DP_X0_PRED_SAMPLE) x = nullptr;
     const unsigned long long bytes = 4ull * (unsigned long long)B * (unsigned long long)n, sbytes = 16ull * (unsigned long long)B;
     const unsigned long long wbytes = (unsigned long long)dp_x0_abs_quantile_workspace(B, n);
-    if (th_overlap(stats, sbytes, x, bytes) || th_overlap(stats, sbytes, m, bytes)) return (int)hipErrorInvalidValue;
-    if (route == DP_X0_ROUTE_MULTI && (th_overlap(ws, wbytes, x, bytes) || th_overlap(ws, wbytes, m, bytes) || th_overlap(ws, wbytes, stats, sbytes)))
+    if (dp_bytes_overlap(stats, sbytes, x, bytes) || dp_bytes_overlap(stats, sbytes, m, bytes)) return (int)hipErrorInvalidValue;
+    if (route == DP_X0_ROUTE_MULTI && (dp_bytes_overlap(ws, wbytes, x, bytes) || dp_bytes_overlap(ws, wbytes, m, bytes) || dp_bytes_overlap(ws, wbytes, stats, sbytes)))
         return (int)hipErrorInvalidValue;
     const void* ptrs[2] = {x, m};
-    const long long head = th_head(n, ptrs, 2);
+    const long long head = th_row_head(n, ptrs, 2);
     const ThRank r = {(unsigned)lo, (unsigned)hi, w, max_value};
     const hipStream_t st = (hipStream_t)stream;
     if (route == DP_X0_ROUTE_LDS) {
@@ -525,13 +477,13 @@ static int th_check_step(const float* x, const float* m, const float* z, const f
     if (mode == DP_X0_MODE_CONVERT && (z || x0_out)) return (int)hipErrorInvalidValue;
     const unsigned long long bytes = 4ull * (unsigned long long)B * (unsigned long long)n, sbytes = 16ull * (unsigned long long)B;
     // the alias the kernels are written for: prev == x.  Everything else is disjoint.
-    if (*need_x && prev != x && th_overlap(prev, bytes, x, bytes)) return (int)hipErrorInvalidValue;
-    if (th_overlap(prev, bytes, m, bytes) || th_overlap(prev, bytes, z, bytes) || th_overlap(prev, bytes, x0_out, bytes)) return (int)hipErrorInvalidValue;
-    if (th_overlap(x0_out, bytes, m, bytes) || th_overlap(x0_out, bytes, z, bytes)) return (int)hipErrorInvalidValue;
-    if (*need_x && th_overlap(x0_out, bytes, x, bytes)) return (int)hipErrorInvalidValue;
+    if (*need_x && prev != x && dp_bytes_overlap(prev, bytes, x, bytes)) return (int)hipErrorInvalidValue;
+    if (dp_bytes_overlap(prev, bytes, m, bytes) || dp_bytes_overlap(prev, bytes, z, bytes) || dp_bytes_overlap(prev, bytes, x0_out, bytes)) return (int)hipErrorInvalidValue;
+    if (dp_bytes_overlap(x0_out, bytes, m, bytes) || dp_bytes_overlap(x0_out, bytes, z, bytes)) return (int)hipErrorInvalidValue;
+    if (*need_x && dp_bytes_overlap(x0_out, bytes, x, bytes)) return (int)hipErrorInvalidValue;
     if (stats && treat == DP_X0_TREAT_THRESHOLD) {
-        if (th_overlap(stats, sbytes, prev, bytes) || th_overlap(stats, sbytes, x0_out, bytes) || th_overlap(stats, sbytes, m, bytes) ||
-            th_overlap(stats, sbytes, z, bytes) || (*need_x && th_overlap(stats, sbytes, x, bytes)))
+        if (dp_bytes_overlap(stats, sbytes, prev, bytes) || dp_bytes_overlap(stats, sbytes, x0_out, bytes) || dp_bytes_overlap(stats, sbytes, m, bytes) ||
+            dp_bytes_overlap(stats, sbytes, z, bytes) || (*need_x && dp_bytes_overlap(stats, sbytes, x, bytes)))
             return (int)hipErrorInvalidValue;
     }
     return 0;
@@ -546,11 +498,9 @@ extern "C" int dp_x0_step(const float* x, const float* m, const float* z, const 
     if (!need_x) x = nullptr;
     if (treat != DP_X0_TREAT_THRESHOLD) stats = nullptr;
     const void* ptrs[5] = {x, m, z, prev, x0_out};
-    const long long head = th_head(n, ptrs, 5);
-    const long long n4 = (n - head) / 4;
-    const long long work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
+    const long long head = th_row_head(n, ptrs, 5);
     ThStep p = {mode, pred, treat, reclip ? 1 : 0, *coef};
-    TH_LAUNCH(th_step_kernel, th_grid(work, B, DP_X0_STEP_MAX_BLOCKS), dim3(256), 0, (hipStream_t)stream, x, m, z, stats, p, prev, x0_out, B, n,
+    TH_LAUNCH(th_step_kernel, th_grid(dp_ht_work(n, head), B, DP_X0_STEP_MAX_BLOCKS), dim3(256), 0, (hipStream_t)stream, x, m, z, stats, p, prev, x0_out, B, n,
               head);
     return DP_LAUNCH_CHECK();
 }
@@ -565,7 +515,7 @@ extern "C" int dp_x0_threshold_step(const float* x, const float* m, const float*
     if (n > DP_THRESHOLD_LDS_MAX || !th_rank_ok(n, lo, hi, w)) return (int)hipErrorInvalidValue;
     if (!need_x) x = nullptr;
     const void* ptrs[5] = {x, m, z, prev, x0_out};
-    const long long head = th_head(n, ptrs, 5);
+    const long long head = th_row_head(n, ptrs, 5);
     ThStep p = {mode, pred, DP_X0_TREAT_THRESHOLD, reclip ? 1 : 0, *coef};
     const ThRank r = {(unsigned)lo, (unsigned)hi, w, max_value};
     TH_LAUNCH((th_lds_kernel<true>), dim3((unsigned)B), dim3(TH_LDS_THREADS), 0, (hipStream_t)stream, x, m, z, p, r, prev, x0_out, stats, n,

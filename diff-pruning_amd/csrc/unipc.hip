@@ -26,7 +26,7 @@
 //
 // Memory bound: 4 (2 + [PC > 0] + max(PC, PP - 1)) B read and 4 (2 + [PC > 0]) B written per element, 16-byte accesses, nothing else.
 // Plain vector loads and stores.
-#include "dp_common.h"
+#include "dp_headtail.h"
 
 // The launch macro of this file: the body of the library's own (dp_common.h) under a name of its own, so that the launch sites of
 // this file are tabled by this file's test module (tests/test_unipc_gpu.py), as dpm_solver.hip, stage.hip and evalmetrics.hip do.
@@ -86,56 +86,36 @@ __device__ __forceinline__ void unipc_one(float e, float xp, float xl, float m0,
     xn = v;
 }
 
-// Elements [0, head) and [head + 4 * n4, n) take 4-byte accesses, the n4 = (n - head) / 4 groups between them 16-byte ones.  The
-// launcher chooses head so that every pointer + head is 16-byte aligned, or head = n when the pointers do not share one alignment.
-// No __restrict__ on the pointers that may alias (header); e aliases no output.  NH = max(PC, PP - 1) history buffers are read,
+// The head / body / tail loop of dp_headtail.h.  No __restrict__ on the pointers that may alias (header); e aliases no output.  NH = max(PC, PP - 1) history buffers are read,
 // x_last only when PC > 0; x_c is written only when PC > 0.
 template <int PC, int PP, bool X0>
 __global__ __launch_bounds__(256) void unipc_step_kernel(const float* __restrict__ e, const float* x_pred, const float* x_last,
                                                          const float* m0, const float* m1, const float* m2, dp_unipc_coef c,
                                                          float* m_new, float* x_c, float* x_next, long long n, long long head) {
     constexpr int NH = PC > PP - 1 ? PC : PP - 1;
-    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long stride = (long long)gridDim.x * 256;
-    const long long n4 = (n - head) / 4;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long i = tid; i < n4; i += stride) {
-        const long long at = head + 4 * i;
-        const float4 ev = *reinterpret_cast<const float4*>(e + at);
-        const float4 pv = *reinterpret_cast<const float4*>(x_pred + at);
-        const float4 lv = PC > 0 ? *reinterpret_cast<const float4*>(x_last + at) : zero;
-        const float4 av = NH >= 1 ? *reinterpret_cast<const float4*>(m0 + at) : zero;
-        const float4 bv = NH >= 2 ? *reinterpret_cast<const float4*>(m1 + at) : zero;
-        const float4 cv = NH >= 3 ? *reinterpret_cast<const float4*>(m2 + at) : zero;
-        float4 mv, xc, xn;
-        unipc_one<PC, PP, X0>(ev.x, pv.x, lv.x, av.x, bv.x, cv.x, c, mv.x, xc.x, xn.x);
-        unipc_one<PC, PP, X0>(ev.y, pv.y, lv.y, av.y, bv.y, cv.y, c, mv.y, xc.y, xn.y);
-        unipc_one<PC, PP, X0>(ev.z, pv.z, lv.z, av.z, bv.z, cv.z, c, mv.z, xc.z, xn.z);
-        unipc_one<PC, PP, X0>(ev.w, pv.w, lv.w, av.w, bv.w, cv.w, c, mv.w, xc.w, xn.w);
-        *reinterpret_cast<float4*>(m_new + at) = mv;                 // after every load of this lane's elements
-        if (PC > 0) *reinterpret_cast<float4*>(x_c + at) = xc;
-        *reinterpret_cast<float4*>(x_next + at) = xn;
-    }
-    const long long ns = n - 4 * n4;                  // the scalar head and tail (everything when head == n)
-    for (long long j = tid; j < ns; j += stride) {
-        const long long i = j < head ? j : 4 * n4 + j;
-        const float es = e[i], ps = x_pred[i];
-        const float ls = PC > 0 ? x_last[i] : 0.f;
-        const float as = NH >= 1 ? m0[i] : 0.f;
-        const float bs = NH >= 2 ? m1[i] : 0.f;
-        const float cs = NH >= 3 ? m2[i] : 0.f;
-        float mn, xc, xn;
-        unipc_one<PC, PP, X0>(es, ps, ls, as, bs, cs, c, mn, xc, xn);
-        m_new[i] = mn;
-        if (PC > 0) x_c[i] = xc;
-        x_next[i] = xn;
-    }
-}
-
-// [a, a + 4 n) and [b, b + 4 n) share a byte (the same buffer included)
-static inline bool up_overlap(const void* a, const void* b, long long n) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b, len = 4ull * (unsigned long long)n;
-    return a0 < b0 + len && b0 < a0 + len;
+    dp_ht_for(
+        n, head, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256,
+        [&](long long at) {
+            const float4 ev = dp_ld4(e, at, true), pv = dp_ld4(x_pred, at, true), lv = dp_ld4(x_last, at, PC > 0);
+            const float4 av = dp_ld4(m0, at, NH >= 1), bv = dp_ld4(m1, at, NH >= 2), cv = dp_ld4(m2, at, NH >= 3);
+            float4 mv, xc, xn;
+            unipc_one<PC, PP, X0>(ev.x, pv.x, lv.x, av.x, bv.x, cv.x, c, mv.x, xc.x, xn.x);
+            unipc_one<PC, PP, X0>(ev.y, pv.y, lv.y, av.y, bv.y, cv.y, c, mv.y, xc.y, xn.y);
+            unipc_one<PC, PP, X0>(ev.z, pv.z, lv.z, av.z, bv.z, cv.z, c, mv.z, xc.z, xn.z);
+            unipc_one<PC, PP, X0>(ev.w, pv.w, lv.w, av.w, bv.w, cv.w, c, mv.w, xc.w, xn.w);
+            dp_st4(m_new, at, mv);                                   // after every load of this lane's elements
+            if (PC > 0) dp_st4(x_c, at, xc);
+            dp_st4(x_next, at, xn);
+        },
+        [&](long long i) {
+            const float es = e[i], ps = x_pred[i], ls = dp_ld1(x_last, i, PC > 0);
+            const float as = dp_ld1(m0, i, NH >= 1), bs = dp_ld1(m1, i, NH >= 2), cs = dp_ld1(m2, i, NH >= 3);
+            float mn, xc, xn;
+            unipc_one<PC, PP, X0>(es, ps, ls, as, bs, cs, c, mn, xc, xn);
+            m_new[i] = mn;
+            if (PC > 0) x_c[i] = xc;
+            x_next[i] = xn;
+        });
 }
 
 extern "C" int dp_unipc_step(const float* e, const float* x_pred, const float* x_last, const float* m0, const float* m1,
@@ -152,29 +132,19 @@ extern "C" int dp_unipc_step(const float* e, const float* x_pred, const float* x
     // the aliases the kernel is written for: m_new == m0 | m1 | m2, x_c == x_last, x_next == x_pred.  Everything else is disjoint.
     const void* ins[6] = {e, x_pred, x_last, hist[0], hist[1], hist[2]};
     const void* outs[3] = {m_new, x_c, x_next};
+    const unsigned long long len = 4ull * (unsigned long long)n;
     for (int o = 0; o < 3; o++) {
-        if (!outs[o]) continue;
         for (int p = o + 1; p < 3; p++)
-            if (outs[p] && up_overlap(outs[o], outs[p], n)) return (int)hipErrorInvalidValue;
+            if (dp_bytes_overlap(outs[o], len, outs[p], len)) return (int)hipErrorInvalidValue;
         for (int i = 0; i < 6; i++) {
-            if (!ins[i] || !up_overlap(outs[o], ins[i], n)) continue;
+            if (!dp_bytes_overlap(outs[o], len, ins[i], len)) continue;
             const bool allowed = outs[o] == ins[i] && ((o == 0 && i >= 3) || (o == 1 && i == 2) || (o == 2 && i == 1));
             if (!allowed) return (int)hipErrorInvalidValue;
         }
     }
-    // one alignment for every pointer -> a scalar head of 0 .. 3 elements brings all of them to 16 bytes; otherwise all scalar
-    const uintptr_t a = (uintptr_t)e & 15;
-    bool same = (a & 3) == 0;
-    for (int i = 0; i < 6; i++)
-        if (ins[i]) same = same && ((uintptr_t)ins[i] & 15) == a;
-    for (int o = 0; o < 3; o++)
-        if (outs[o]) same = same && ((uintptr_t)outs[o] & 15) == a;
-    long long head = same ? (long long)(((16 - a) & 15) / 4) : n;
-    if (head > n) head = n;
-    const long long n4 = (n - head) / 4;
-    const long long work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
-    const long long nb = (work + 255) / 256;
-    const unsigned grid = (unsigned)(nb > DP_UNIPC_MAX_BLOCKS ? DP_UNIPC_MAX_BLOCKS : nb < 1 ? 1 : nb);
+    const void* ptrs[9] = {e, x_pred, x_last, hist[0], hist[1], hist[2], m_new, x_c, x_next};
+    const long long head = dp_ht_head(n, ptrs, 9);
+    const unsigned grid = dp_ht_blocks(n, head, DP_UNIPC_MAX_BLOCKS);
     const dp_unipc_coef c = *coef;
     const hipStream_t st = (hipStream_t)stream;
     m0 = hist[0]; m1 = hist[1]; m2 = hist[2];

@@ -18,6 +18,7 @@
 //
 // Plain vector loads and stores, 64-bit element indices.
 #include "dp_common.h"
+#include "dp_headtail_plan.h"                  // dp_bytes_overlap
 
 // The launch macro of this file: the body of the library's own (dp_common.h) under a name of its own, so that the launch sites of
 // this file are tabled by this file's test module (tests/test_vae_gpu.py), as unipc.hip, dpm_solver.hip and stage.hip do.
@@ -154,13 +155,6 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(float* b, int planes, i
     }
 }
 
-// [a, a + na) and [b, b + nb) share a byte (the same buffer included); a null pointer overlaps nothing
-static inline bool vae_overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 static inline int post_blocks_per_image(int N, long long work) {
     const int ny = N < DP_VAE_MAX_BLOCKS ? N : DP_VAE_MAX_BLOCKS;
     const long long cap = DP_VAE_MAX_BLOCKS / ny > 1 ? DP_VAE_MAX_BLOCKS / ny : 1;
@@ -186,9 +180,9 @@ extern "C" int dp_gaussian_posterior(const float* moments, long long m_stride, i
     for (int o = 0; o < 6; o++) {
         if (!outs[o]) continue;
         for (int p = o + 1; p < 6; p++)
-            if (vae_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return (int)hipErrorInvalidValue;
-        if (vae_overlap(outs[o], out_bytes[o], moments, m_bytes)) return (int)hipErrorInvalidValue;
-        if (vae_overlap(outs[o], out_bytes[o], noise, plane) && !(o == 3 && (const void*)z == (const void*)noise)) return (int)hipErrorInvalidValue;
+            if (dp_bytes_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return (int)hipErrorInvalidValue;
+        if (dp_bytes_overlap(outs[o], out_bytes[o], moments, m_bytes)) return (int)hipErrorInvalidValue;
+        if (dp_bytes_overlap(outs[o], out_bytes[o], noise, plane) && !(o == 3 && (const void*)z == (const void*)noise)) return (int)hipErrorInvalidValue;
     }
     bool vec = chw % 4 == 0 && (N == 1 || m_stride % 4 == 0) && ((uintptr_t)moments & 15) == 0 && ((uintptr_t)noise & 15) == 0;
     for (int o = 0; o < 4; o++) vec = vec && ((uintptr_t)outs[o] & 15) == 0;
@@ -214,8 +208,8 @@ extern "C" int dp_tile_blend(float* b, int planes, int Hb, int Wb, const float* 
         return (int)hipErrorInvalidValue;
     const unsigned long long P = (unsigned long long)planes;
     const unsigned long long nb = 4ull * P * Hb * Wb, na = 4ull * P * Ha * Wb, nl = 4ull * P * Hb * Wl, no = out ? 4ull * P * Hout * Wout : 0;
-    if (vae_overlap(b, nb, a, na) || vae_overlap(b, nb, l, nl) || vae_overlap(b, nb, out, no) || vae_overlap(out, no, a, na) ||
-        vae_overlap(out, no, l, nl))
+    if (dp_bytes_overlap(b, nb, a, na) || dp_bytes_overlap(b, nb, l, nl) || dp_bytes_overlap(b, nb, out, no) || dp_bytes_overlap(out, no, a, na) ||
+        dp_bytes_overlap(out, no, l, nl))
         return (int)hipErrorInvalidValue;
     if (!a && !l && !out) return 0;                                   // nothing to blend and nowhere to put it
     const long long hw = (long long)Hb * Wb;

@@ -53,25 +53,18 @@ class _SchedulerBase:
         from . import checkpoint
         checkpoint.save_scheduler(self, save_directory)
 
-    def _init_tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule):
-        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.init_noise_sigma = 1.0
-        self._acp_dev = {}
+    @classmethod
+    def from_config(cls, config):
+        d = vars(config) if not isinstance(config, dict) else config
+        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
 
-    def _init_solver_tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule):
-        """The alpha_t / sigma_t / lambda_t tables of the multistep solvers (scheduling_dpmsolver_multistep.py:158-176,
-        scheduling_unipc_multistep.py:144-167), sqrt and log correctly rounded (_rounded_once)."""
-        if beta_schedule == 'squaredcos_cap_v2':
-            self.betas = _betas_for_alpha_bar(num_train_timesteps)
-        else:
-            self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
+    def scale_model_input(self, sample, *args, **kwargs):
+        return sample
+
+    def _init_tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule, betas=None):
+        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule) if betas is None else betas
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.alpha_t = _rounded_once(torch.sqrt, self.alphas_cumprod)
-        self.sigma_t = _rounded_once(torch.sqrt, 1 - self.alphas_cumprod)
-        self.lambda_t = _rounded_once(torch.log, self.alpha_t) - _rounded_once(torch.log, self.sigma_t)
         self.init_noise_sigma = 1.0
         self._acp_dev = {}
 
@@ -134,14 +127,6 @@ class DDPMScheduler(_SchedulerBase):
         self.custom_timesteps = False
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
-
-    @classmethod
-    def from_config(cls, config):
-        d = vars(config) if not isinstance(config, dict) else config
-        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
 
     def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None):
         """scheduling_ddpm.py:185-236."""
@@ -273,14 +258,6 @@ class DDIMScheduler(_SchedulerBase):
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
 
-    @classmethod
-    def from_config(cls, config):
-        d = vars(config) if not isinstance(config, dict) else config
-        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
-
     def set_timesteps(self, num_inference_steps, device=None):
         T = self.config.num_train_timesteps
         if num_inference_steps > T:
@@ -367,7 +344,72 @@ def _rounded_once(fn, t):
     return fn(t.double()).float()
 
 
-class DPMSolverMultistepScheduler(_SchedulerBase):
+class _MultistepBase(_SchedulerBase):
+    """What the multistep solvers share, and where a new one starts: the alpha_t / sigma_t / lambda_t tables, the timesteps as a
+    host list beside the `timesteps` tensor (so that `step` reads nothing back from the device), and the history: a ring of
+    `solver_order` device buffers, newest last, that the steps write in turn."""
+    order = 1
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+    def _init_solver_tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule):
+        """scheduling_dpmsolver_multistep.py:158-176, scheduling_unipc_multistep.py:144-167, sqrt and log correctly rounded
+        (_rounded_once)."""
+        self._init_tables(num_train_timesteps, beta_start, beta_end, beta_schedule,
+                          _betas_for_alpha_bar(num_train_timesteps) if beta_schedule == 'squaredcos_cap_v2' else None)
+        self.alpha_t = _rounded_once(torch.sqrt, self.alphas_cumprod)
+        self.sigma_t = _rounded_once(torch.sqrt, 1 - self.alphas_cumprod)
+        self.lambda_t = _rounded_once(torch.log, self.alpha_t) - _rounded_once(torch.log, self.sigma_t)
+
+    def _reset_history(self):
+        """Hook of _set_list: what a solver keeps between steps beside model_outputs and lower_order_nums."""
+
+    def _set_list(self, ts, device=None):
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._ts = [int(v) for v in ts]                               # the host's copy: what `step` looks timesteps up in
+        self._index = {}
+        for i, v in enumerate(self._ts):
+            self._index.setdefault(v, i)
+        self.model_outputs = [None] * self.config.solver_order        # newest last, as the reference keeps them
+        self.lower_order_nums = 0
+        self._reset_history()
+
+    def _rounded_linspace(self, top, num_inference_steps):
+        return np.linspace(0, top, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+
+    def _set_unique(self, ts, device):
+        """Duplicates removed in order of appearance, the history reset."""
+        _, unique_indices = np.unique(ts, return_index=True)
+        ts = ts[np.sort(unique_indices)]
+        self._set_list(ts, device)
+        self.num_inference_steps = len(ts)
+
+    def _begin_step(self, timestep):
+        """(ts, last, t, i, prev_t): the host's timestep list and its last index, this step's timestep, its index (the last one for
+        a timestep that is not in the list) and the timestep after it (0 after the last)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        ts = self._ts
+        last = len(ts) - 1
+        t = int(timestep)
+        i = self._index.get(t, last)
+        return ts, last, t, i, 0 if i == last else ts[i + 1]
+
+    def _oldest_buffer(self, sample):
+        """The oldest buffer of the ring, which takes this step's converted output; a new one where it does not fit `sample`."""
+        buf = self.model_outputs[0]
+        if buf is None or buf.shape != sample.shape or buf.device != sample.device:
+            buf = torch.empty_like(sample)
+        return buf
+
+    def _push_output(self, m):
+        self.model_outputs = self.model_outputs[1:] + [m]
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+
+
+class DPMSolverMultistepScheduler(_MultistepBase):
     """scheduling_dpmsolver_multistep.py:58-707, the deterministic multistep DPM-Solver / DPM-Solver++ of orders 1 .. 3 for epsilon
     models.  The tables and every per-step scalar are 0-d fp32 torch arithmetic on the CPU in the reference's operation order
     (:420-423, :466-473, :557-572), with sqrt, log and exp correctly rounded (_rounded_once: the reference's bits on a host whose
@@ -376,7 +418,6 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     reads nothing back from the device.  The history is a ring of `solver_order` device buffers that the steps write in turn.
     Not carried (NotImplementedError): the SDE variants, dynamic thresholding, `sample` / `v_prediction` models, models that
     predict a variance, `trained_betas`."""
-    order = 1
     _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'solver_order',
                     'prediction_type', 'thresholding', 'dynamic_thresholding_ratio', 'sample_max_value', 'algorithm_type',
                     'solver_type', 'lower_order_final', 'use_karras_sigmas', 'lambda_min_clipped', 'variance_type')
@@ -414,26 +455,6 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         self._set_list(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
         self.use_karras_sigmas = use_karras_sigmas
 
-    @classmethod
-    def from_config(cls, config):
-        d = vars(config) if not isinstance(config, dict) else config
-        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
-
-    def __len__(self):
-        return self.config.num_train_timesteps
-
-    def scale_model_input(self, sample, *args, **kwargs):
-        return sample
-
-    def _set_list(self, ts, device=None):
-        self.timesteps = torch.from_numpy(ts).to(device)
-        self._ts = [int(v) for v in ts]                               # the host's copy: what `step` looks timesteps up in
-        self._index = {}
-        for i, v in enumerate(self._ts):
-            self._index.setdefault(v, i)
-        self.model_outputs = [None] * self.config.solver_order        # newest last, as the reference keeps them
-        self.lower_order_nums = 0
-
     def _sigma_to_t(self, sigma, log_sigmas):
         """:285-306 for one sigma: the fractional index at which log sigma lies between two neighbours of the table."""
         log_sigma = np.log(sigma)
@@ -457,18 +478,14 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         """:208-247: the lambda_min_clipped search, the rounded linspace (or the Karras sigmas mapped back to timesteps), duplicates
         removed in order of appearance, the history reset."""
         clipped_idx = int(torch.searchsorted(torch.flip(self.lambda_t, [0]), self.config.lambda_min_clipped))
-        ts = (np.linspace(0, self.config.num_train_timesteps - 1 - clipped_idx, num_inference_steps + 1)
-              .round()[::-1][:-1].copy().astype(np.int64))
+        ts = self._rounded_linspace(self.config.num_train_timesteps - 1 - clipped_idx, num_inference_steps)
         if self.use_karras_sigmas:
             sigmas = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
             log_sigmas = np.log(sigmas)
             sigmas = self._convert_to_karras(in_sigmas=sigmas, num_inference_steps=num_inference_steps)
             ts = np.array([self._sigma_to_t(sigma, log_sigmas) for sigma in sigmas]).round()
             ts = np.flip(ts).copy().astype(np.int64)
-        _, unique_indices = np.unique(ts, return_index=True)
-        ts = ts[np.sort(unique_indices)]
-        self._set_list(ts, device)
-        self.num_inference_steps = len(ts)
+        self._set_unique(ts, device)
 
     def step_coefs(self, order, timestep, prev_timestep, s1=None, s2=None):
         """The fp32 scalars of one update as ops.dpm_solver_step names them, formed as :351, :420-427, :466-501 and :557-588 form
@@ -515,15 +532,9 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     def step(self, model_output, timestep, sample, generator=None, return_dict=True):
         """:591-667.  The order is the reference's choice (solver_order, the lower_order_nums warm-up, lower_order_final /
         lower_order_second below 15 steps); exactly one launch, nothing read back."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        ts, last, t, i, prev_t = self._begin_step(timestep)
         if model_output.shape[1] != sample.shape[1]:
             raise NotImplementedError('learned-variance models are not part of this path')
-        ts = self._ts
-        last = len(ts) - 1
-        t = int(timestep)
-        i = self._index.get(t, last)
-        prev_t = 0 if i == last else ts[i + 1]
         final = i == last and self.config.lower_order_final and len(ts) < 15
         second = i == last - 1 and self.config.lower_order_final and len(ts) < 15
         so = self.config.solver_order
@@ -536,21 +547,17 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         coef = self.step_coefs(order, t, prev_t, ts[i - 1] if order >= 2 else None, ts[i - 2] if order == 3 else None)
         sample = sample.contiguous()
         hist = self.model_outputs
-        buf = hist[0]                                                 # the oldest buffer of the ring takes this step's m0
-        if buf is None or buf.shape != sample.shape or buf.device != sample.device:
-            buf = torch.empty_like(sample)
         prev, m0 = ops.dpm_solver_step(sample, model_output.contiguous(), coef, order=order,
                                        data_pred=self.config.algorithm_type == 'dpmsolver++',
-                                       m1=hist[-1] if order >= 2 else None, m2=hist[-2] if order == 3 else None, m0_out=buf)
-        self.model_outputs = hist[1:] + [m0]
-        if self.lower_order_nums < so:
-            self.lower_order_nums += 1
+                                       m1=hist[-1] if order >= 2 else None, m2=hist[-2] if order == 3 else None,
+                                       m0_out=self._oldest_buffer(sample))
+        self._push_output(m0)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev)
 
 
-class UniPCMultistepScheduler(_SchedulerBase):
+class UniPCMultistepScheduler(_MultistepBase):
     """scheduling_unipc_multistep.py:60-641, the UniPC predictor-corrector of orders 1 .. 3 (B(h) forms bh1 / bh2) for epsilon
     models.  The corrector of a step reuses the model evaluation the next predictor needs, so `step` runs, in the reference's order,
     convert_model_output, the UniC update of the PREVIOUS step's order on the old history and `last_sample`, and the UniP update
@@ -563,7 +570,6 @@ class UniPCMultistepScheduler(_SchedulerBase):
     model's output buffer is written.
     Not carried (NotImplementedError): dynamic thresholding, `solver_p`, `trained_betas`, `sample` / `v_prediction` models,
     solver_order above 3, models that predict a variance."""
-    order = 1
     _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'solver_order',
                     'prediction_type', 'thresholding', 'dynamic_thresholding_ratio', 'sample_max_value', 'predict_x0',
                     'solver_type', 'lower_order_final', 'disable_corrector', 'solver_p')
@@ -604,36 +610,13 @@ class UniPCMultistepScheduler(_SchedulerBase):
         self._xc = None                                               # the corrected sample's buffer (last_sample after a corrector)
         self._set_list(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
 
-    @classmethod
-    def from_config(cls, config):
-        d = vars(config) if not isinstance(config, dict) else config
-        return cls(**{k: d[k] for k in cls._CONFIG_KEYS if k in d})
-
-    def __len__(self):
-        return self.config.num_train_timesteps
-
-    def scale_model_input(self, sample, *args, **kwargs):
-        return sample
-
-    def _set_list(self, ts, device=None):
-        self.timesteps = torch.from_numpy(ts).to(device)
-        self._ts = [int(v) for v in ts]                               # the host's copy: what `step` looks timesteps up in
-        self._index = {}
-        for i, v in enumerate(self._ts):
-            self._index.setdefault(v, i)
-        self.model_outputs = [None] * self.config.solver_order        # newest last, as the reference keeps them
-        self.lower_order_nums = 0
+    def _reset_history(self):
         self.last_sample = None
 
     def set_timesteps(self, num_inference_steps, device=None):
         """:187-219: the rounded linspace, duplicates removed in order of appearance, the history reset (timestep_list is kept,
         as the reference keeps it)."""
-        ts = (np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps + 1)
-              .round()[::-1][:-1].copy().astype(np.int64))
-        _, unique_indices = np.unique(ts, return_index=True)
-        ts = ts[np.sort(unique_indices)]
-        self._set_list(ts, device)
-        self.num_inference_steps = len(ts)
+        self._set_unique(self._rounded_linspace(self.config.num_train_timesteps - 1, num_inference_steps), device)
 
     def update_coefs(self, order, s0, t, sis, corrector):
         """The fp32 scalars of one UniP (:339-407) or UniC (:443-514) update of `order` from s0 to t, formed as the reference forms
@@ -697,18 +680,12 @@ class UniPCMultistepScheduler(_SchedulerBase):
         """:518-600.  The corrector's order is the previous step's `this_order`, the predictor's the reference's choice
         (solver_order, the steps that remain under lower_order_final, the lower_order_nums warm-up); exactly one launch, nothing
         read back."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        ts, last, t, i, prev_t = self._begin_step(timestep)
         if model_output.shape[1] != sample.shape[1]:
             raise NotImplementedError('a model output of %d channels for a sample of %d (a predicted variance) is not part of this path'
                                       % (model_output.shape[1], sample.shape[1]))
-        ts = self._ts
-        last = len(ts) - 1
-        t = int(timestep)
-        i = self._index.get(t, last)
         use_corrector = i > 0 and i - 1 not in self.disable_corrector and self.last_sample is not None
         pc = self.this_order if use_corrector else 0
-        prev_t = 0 if i == last else ts[i + 1]
         so = self.config.solver_order
         this_order = min(so, len(ts) - i) if self.config.lower_order_final else so
         pp = min(this_order, self.lower_order_nums + 1)
@@ -716,8 +693,8 @@ class UniPCMultistepScheduler(_SchedulerBase):
         coef = self.step_coefs(pc, pp, t, prev_t, self.timestep_list)
         sample = sample.contiguous()
         hist = self.model_outputs
-        buf = hist[0]                                                 # the oldest buffer of the ring takes this step's output
-        if buf is None or buf.shape != sample.shape or buf.device != sample.device or any(buf is h for h in hist[1:]):
+        buf = self._oldest_buffer(sample)
+        if any(buf is h for h in hist[1:]):
             buf = torch.empty_like(sample)
         xc = None
         if pc:
@@ -727,12 +704,10 @@ class UniPCMultistepScheduler(_SchedulerBase):
         prev, xc, m_new = ops.unipc_step(model_output.contiguous(), sample, coef, pc=pc, pp=pp, predict_x0=self.predict_x0,
                                          x_last=self.last_sample if pc else None, hist=hist[::-1][:max(pc, pp - 1)],
                                          m_new=buf, x_c=xc)
-        self.model_outputs = hist[1:] + [m_new]
+        self._push_output(m_new)
         self.timestep_list = list(self.timestep_list[1:]) + [t]
         self.this_order = pp
         self.last_sample = xc if pc else sample
-        if self.lower_order_nums < so:
-            self.lower_order_nums += 1
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev)

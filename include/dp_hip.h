@@ -522,6 +522,14 @@ int dp_ddim_step(const float* x, const float* eps, const float* vnoise, float a_
 int dp_ddpm_step(const float* x, const float* eps, const float* vnoise, float sqrt_a_t, float sqrt_b_t, float c_x0,
                  float c_xt, float sigma, int clip, float clip_range, float* out, long long n, void* stream);
 
+/* ---- The head / body / tail access rule of the elementwise step launchers below (dp_denoise_step, dp_cfg_denoise_step,
+ * dp_dpm_solver_step, dp_unipc_step, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
+ * When every pointer in use (a NULL or unread one does not count) shares one 4-byte-aligned phase modulo 16, a scalar head of
+ * 0 .. 3 elements brings all of them to 16 bytes: the n4 = (n - head) / 4 groups after it take 16-byte accesses, the head and the
+ * n - head - 4 n4 tail elements 4-byte ones.  Otherwise every access is 4 bytes (head = n).  Any n: long long indexing, one lane
+ * per group (or per scalar element, whichever are more) in blocks of 256 lanes, grid-stride beyond the launcher's
+ * DP_*_MAX_BLOCKS.  The results do not depend on the width. */
+
 /* One update of the ddpm_exp sampler (csrc/sampler.hip; ddpm_exp/functions/denoising.py) over n fp32 elements, one pass:
  *   mode 0, generalized_steps:23-29:  x0 = (x - eps * p0) / p1;              next = p2 * x0 + p3 * z + p4 * eps
  *           (p0 .. p4 = sqrt(1 - a_t), sqrt(a_t), sqrt(a_next), c1, c2; p5 unread)
@@ -529,9 +537,8 @@ int dp_ddpm_step(const float* x, const float* eps, const float* vnoise, float sq
  *           (p0 .. p5 = sqrt(1 / a_t), sqrt(1 / a_t - 1), sqrt(a_next) * beta_t, sqrt(1 - beta_t) * (1 - a_next), 1 - a_t, sigma)
  * every operation rounded separately, in the reference's order, with a true division; the scalars are the host's 0-d fp32
  * arithmetic.  z == NULL: no noise term (eta = 0, where c1 is exactly 0; the t = 0 mask).  x0_out != NULL: the x0 prediction is
- * written in the same pass.  `next` may be `x`; x0_out aliases nothing.  16-byte accesses between a scalar head and tail when all
- * pointers share one alignment modulo 16, 4-byte accesses otherwise; any n (long long indexing, grid-stride beyond
- * DP_DENOISE_MAX_BLOCKS blocks of 256 lanes). */
+ * written in the same pass.  `next` may be `x`; x0_out aliases nothing.  Accesses: the head / body / tail rule above, at most
+ * DP_DENOISE_MAX_BLOCKS blocks. */
 #define DP_DENOISE_MAX_BLOCKS 4096
 int dp_denoise_step(const float* x, const float* eps, const float* z, int mode, float p0, float p1, float p2, float p3, float p4,
                     float p5, float* next, float* x0_out, long long n, void* stream);
@@ -556,9 +563,8 @@ int dp_image_to_u8(const float* x, long long x_img_stride, int N, int C, int H, 
  *   next = (sqrt_a_prev * x0 + c_dir * e') + (sigma * z) * temperature          z == NULL: no noise term
  * every operation rounded separately, true divisions; the scalars are the host's (ldm_sampler.sampling_tables).  x0_out / eg_out
  * != NULL: the x0 prediction / the guided eps e_g are written in the same pass.  `next` may be `x`; x0_out and eg_out alias
- * nothing.  A history pointer the order does not read may be NULL.  16-byte accesses between a scalar head and tail when all
- * pointers in use share one alignment modulo 16, 4-byte accesses otherwise; any n (long long indexing, grid-stride beyond
- * DP_DENOISE_MAX_BLOCKS blocks of 256 lanes). */
+ * nothing.  A history pointer the order does not read may be NULL.  Accesses: the head / body / tail rule above, at most
+ * DP_DENOISE_MAX_BLOCKS blocks. */
 int dp_cfg_denoise_step(const float* x, const float* e_u, const float* e_c, float scale, int order, const float* h1, const float* h2,
                         const float* h3, float s1m, float sqrt_a_t, float sqrt_a_prev, float c_dir, float sigma, float temperature,
                         const float* z, float* next, float* x0_out, float* eg_out, long long n, void* stream);
@@ -579,8 +585,7 @@ int dp_cfg_denoise_step(const float* x, const float* e_u, const float* e_c, floa
  * buffers that this very step still reads: each lane reads every input of its elements before it writes any of them, and no
  * other lane touches them.  Any other overlap between an output and another buffer is hipErrorInvalidValue, as are a null required
  * pointer and an order outside 1 .. 3; n <= 0 is a no-op.
- * 16-byte accesses between a scalar head and tail when all pointers in use share one alignment modulo 16, 4-byte accesses
- * otherwise; any n (long long indexing, grid-stride beyond DP_DPM_SOLVER_MAX_BLOCKS blocks of 256 lanes). */
+ * Accesses: the head / body / tail rule above, at most DP_DPM_SOLVER_MAX_BLOCKS blocks. */
 #define DP_DPM_SOLVER_MAX_BLOCKS 4096
 typedef struct dp_dpm_solver_coef {
     float sigma_s, alpha_s;             /* convert (data_pred only) */
@@ -608,8 +613,7 @@ int dp_dpm_solver_step(const float* x, const float* e, const float* m1, const fl
  * step may still read), `x_c` may be `x_last` itself, `x_next` may be `x_pred` itself: each lane reads every input of its elements
  * before it writes any of them, and no other lane touches them.  Any other overlap between an output and another buffer is
  * hipErrorInvalidValue, as are a null required pointer, pc outside 0 .. 3 and pp outside 1 .. 3: nothing is launched.  n <= 0 is a no-op.
- * 16-byte accesses between a scalar head and tail when all pointers in use share one alignment modulo 16, 4-byte accesses
- * otherwise; any n (long long indexing, grid-stride beyond DP_UNIPC_MAX_BLOCKS blocks of 256 lanes). */
+ * Accesses: the head / body / tail rule above, at most DP_UNIPC_MAX_BLOCKS blocks. */
 #define DP_UNIPC_MAX_BLOCKS 4096
 typedef struct dp_unipc_coef {
     float sigma_s, alpha_s;             /* convert (predict_x0 only) */
@@ -641,8 +645,8 @@ int dp_unipc_step(const float* e, const float* x_pred, const float* x_last, cons
  *   DP_X0_MODE_DDIM: prev = c0 x0 + c1 eps [+ cz z];  _DDPM: prev = (c0 x0 + c1 x) + (cz z, or 0 without z);
  *   _CONVERT: prev = the treated x0 (z and x0_out must be NULL; x may be NULL for a sample model).
  * x0_out (optional) takes the treated x0.  prev may be x itself; any other overlap between an output (or stats) and another buffer is
- * hipErrorInvalidValue.  16-byte accesses between a scalar head and tail when n % 4 == 0 and all pointers in use share one alignment
- * modulo 16, 4-byte accesses otherwise; at most DP_X0_STEP_MAX_BLOCKS blocks of 256 lanes, strided over rows and images beyond.
+ * hipErrorInvalidValue.  Accesses: the head / body / tail rule above within every row when n % 4 == 0 (then every row has the
+ * first one's phase), 4-byte accesses otherwise; at most DP_X0_STEP_MAX_BLOCKS blocks of 256 lanes, strided over rows and images beyond.
  *
  * dp_x0_threshold_step: the LDS route of the quantile with the thresholded step applied by the same workgroup, ONE launch for
  * n <= DP_THRESHOLD_LDS_MAX; writes prev, x0_out (optional) and stats; the bits of dp_x0_abs_quantile followed by dp_x0_step. */
