@@ -15,6 +15,8 @@ The reference hands a pruned UNet to the finetune / sampling scripts as a whole-
   LayerNorm takes the shapes found in the checkpoint, then the coupling graph is checked for consistency.
 
 Host-side only: tensors are plain torch tensors on any device; nothing here touches the HIP kernels."""
+import functools
+import importlib
 import json
 import os
 
@@ -32,12 +34,15 @@ def _config_dict(model):
     return {k: (list(v) if isinstance(v, tuple) else v) for k, v in cfg.items()}
 
 
+# class name -> (module that defines it, imported on first use; the folder a Diffusers pipeline directory keeps it in; whether an
+# LDMPipeline takes it as its first stage).  UNetModel is the CompVis class: it has no Diffusers directory form.
+MODELS = {'UNet2DModel': ('unet', 'unet', False), 'VQModel': ('vq', 'vqvae', True), 'AutoencoderKL': ('vae', 'vae', True),
+          'UNetModel': ('ldm', None, False)}
+_FIRST_STAGES = tuple(n for n, row in MODELS.items() if row[2])
+
+
 def _build(kind, cfg):
-    if kind == 'UNetModel':
-        from .ldm import UNetModel
-        return UNetModel(**cfg)
-    from .unet import UNet2DModel
-    return UNet2DModel(**cfg)
+    return getattr(importlib.import_module('.' + MODELS[kind][0], __package__), kind)(**cfg)
 
 
 def save_pruned(model, directory, pruning_history):
@@ -287,22 +292,31 @@ def _load_weights(d):
     raise FileNotFoundError('no %s in %s' % (' / '.join(_UNET_WEIGHTS), d))
 
 
-def load_unet(directory, subfolder=None):
-    """UNet2DModel.from_pretrained: `directory` (or its `subfolder`) holds config.json + the weight file."""
-    from .unet import UNet2DModel
+def _a(name):                               # 'a VQModel', 'an AutoencoderKL'
+    return ('an ' if name[0] == 'A' else 'a ') + name
+
+
+def load_model(class_name, directory, subfolder=None):
+    """<Class>.from_pretrained: `directory` (or its `subfolder`, or the class's own pipeline folder in it) holds config.json + the
+    weight file; deprecated attention names are converted as modeling_utils.py:809-851 does.  A config.json that names another
+    class is refused."""
     d = os.path.join(directory, subfolder) if subfolder else directory
-    if not os.path.exists(os.path.join(d, 'config.json')) and os.path.exists(os.path.join(d, 'unet', 'config.json')):
-        d = os.path.join(d, 'unet')
-    cfg = {k: v for k, v in _read_json(os.path.join(d, 'config.json')).items() if not k.startswith('_')}
-    model = UNet2DModel(**cfg)
+    folder = MODELS[class_name][1]
+    if not os.path.exists(os.path.join(d, 'config.json')) and os.path.exists(os.path.join(d, folder, 'config.json')):
+        d = os.path.join(d, folder)
+    raw = _read_json(os.path.join(d, 'config.json'))
+    if raw.get('_class_name', class_name) != class_name:
+        raise ValueError('%s holds %s, not %s' % (d, _a(raw['_class_name']), _a(class_name)))
+    model = _build(class_name, {k: v for k, v in raw.items() if not k.startswith('_')})
     model.load_state_dict(convert_deprecated_attention_keys(_load_weights(d)), strict=True)
     return model.eval()
 
 
-def save_unet(model, directory, safe_serialization=False):
-    """UNet2DModel.save_pretrained layout (the vendored diffusers writes the .bin pickle of the state dict by default)."""
+def save_model(model, directory, safe_serialization=False):
+    """<Class>.save_pretrained layout: config.json + diffusion_pytorch_model.bin (the vendored diffusers writes the .bin pickle of
+    the state dict by default), or .safetensors."""
     os.makedirs(directory, exist_ok=True)
-    cfg = dict(_config_dict(model), _class_name='UNet2DModel', _diffusers_version=DIFFUSERS_VERSION)
+    cfg = dict(_config_dict(model), _class_name=type(model).__name__, _diffusers_version=DIFFUSERS_VERSION)
     _write_json(os.path.join(directory, 'config.json'), cfg)
     sd = {k: v.detach().to('cpu').contiguous() for k, v in model.state_dict().items()}
     if safe_serialization:
@@ -310,6 +324,12 @@ def save_unet(model, directory, safe_serialization=False):
         save_file(sd, os.path.join(directory, _UNET_WEIGHTS[0]))
     else:
         torch.save(sd, os.path.join(directory, _UNET_WEIGHTS[1]))
+
+
+load_unet = functools.partial(load_model, 'UNet2DModel')
+load_vq = functools.partial(load_model, 'VQModel')
+load_vae = functools.partial(load_model, 'AutoencoderKL')
+save_unet = save_vq = save_vae = save_model
 
 
 def load_scheduler(cls, directory, subfolder=None):
@@ -331,63 +351,6 @@ def save_scheduler(scheduler, directory):
     _write_json(os.path.join(directory, 'scheduler_config.json'), cfg)
 
 
-def load_vq(directory, subfolder=None):
-    """VQModel.from_pretrained: `directory` (or its `subfolder`) holds config.json + the weight file; deprecated attention names
-    are converted as modeling_utils.py:809-851 does."""
-    from .vq import VQModel
-    d = os.path.join(directory, subfolder) if subfolder else directory
-    if not os.path.exists(os.path.join(d, 'config.json')) and os.path.exists(os.path.join(d, 'vqvae', 'config.json')):
-        d = os.path.join(d, 'vqvae')
-    cfg = {k: v for k, v in _read_json(os.path.join(d, 'config.json')).items() if not k.startswith('_')}
-    model = VQModel(**cfg)
-    model.load_state_dict(convert_deprecated_attention_keys(_load_weights(d)), strict=True)
-    return model.eval()
-
-
-def save_vq(model, directory, safe_serialization=False):
-    """VQModel.save_pretrained layout (config.json + diffusion_pytorch_model.bin, or .safetensors)."""
-    os.makedirs(directory, exist_ok=True)
-    cfg = dict(_config_dict(model), _class_name='VQModel', _diffusers_version=DIFFUSERS_VERSION)
-    _write_json(os.path.join(directory, 'config.json'), cfg)
-    sd = {k: v.detach().to('cpu').contiguous() for k, v in model.state_dict().items()}
-    if safe_serialization:
-        from safetensors.torch import save_file
-        save_file(sd, os.path.join(directory, _UNET_WEIGHTS[0]))
-    else:
-        torch.save(sd, os.path.join(directory, _UNET_WEIGHTS[1]))
-
-
-def load_vae(directory, subfolder=None):
-    """AutoencoderKL.from_pretrained: `directory` (or its `subfolder`, or its `vae/` folder) holds config.json + the weight file;
-    deprecated attention names are converted as modeling_utils.py:809-851 does."""
-    from .vae import AutoencoderKL
-    d = os.path.join(directory, subfolder) if subfolder else directory
-    if not os.path.exists(os.path.join(d, 'config.json')) and os.path.exists(os.path.join(d, 'vae', 'config.json')):
-        d = os.path.join(d, 'vae')
-    raw = _read_json(os.path.join(d, 'config.json'))
-    if raw.get('_class_name', 'AutoencoderKL') != 'AutoencoderKL':
-        raise ValueError('%s holds a %s, not an AutoencoderKL' % (d, raw['_class_name']))
-    model = AutoencoderKL(**{k: v for k, v in raw.items() if not k.startswith('_')})
-    model.load_state_dict(convert_deprecated_attention_keys(_load_weights(d)), strict=True)
-    return model.eval()
-
-
-def save_vae(model, directory, safe_serialization=False):
-    """AutoencoderKL.save_pretrained layout (config.json + diffusion_pytorch_model.bin, or .safetensors)."""
-    os.makedirs(directory, exist_ok=True)
-    cfg = dict(_config_dict(model), _class_name='AutoencoderKL', _diffusers_version=DIFFUSERS_VERSION)
-    _write_json(os.path.join(directory, 'config.json'), cfg)
-    sd = {k: v.detach().to('cpu').contiguous() for k, v in model.state_dict().items()}
-    if safe_serialization:
-        from safetensors.torch import save_file
-        save_file(sd, os.path.join(directory, _UNET_WEIGHTS[0]))
-    else:
-        torch.save(sd, os.path.join(directory, _UNET_WEIGHTS[1]))
-
-
-_FIRST_STAGES = {'VQModel': (load_vq, save_vq), 'AutoencoderKL': (load_vae, save_vae)}
-
-
 def load_pipeline(cls, directory):
     from . import diffusion
     index = _read_json(os.path.join(directory, 'model_index.json'))
@@ -400,7 +363,7 @@ def load_pipeline(cls, directory):
         name = index['vqvae'][1]                         # the component's own class: VQModel, or AutoencoderKL
         if name not in _FIRST_STAGES:
             raise NotImplementedError('first-stage class %s' % name)
-        parts['vqvae'] = _FIRST_STAGES[name][0](directory, 'vqvae')
+        parts['vqvae'] = load_model(name, directory, 'vqvae')
     return cls(**parts)
 
 
@@ -410,7 +373,7 @@ def save_pipeline(pipeline, directory, safe_serialization=False):
     if getattr(pipeline, 'vqvae', None) is not None:
         name = type(pipeline.vqvae).__name__
         index['vqvae'] = ['diffusers', name]
-        _FIRST_STAGES[name][1](pipeline.vqvae, os.path.join(directory, 'vqvae'), safe_serialization)
+        save_model(pipeline.vqvae, os.path.join(directory, 'vqvae'), safe_serialization)
     _write_json(os.path.join(directory, 'model_index.json'), index)
     save_unet(pipeline.unet, os.path.join(directory, 'unet'), safe_serialization)
     save_scheduler(pipeline.scheduler, os.path.join(directory, 'scheduler'))

@@ -19,7 +19,8 @@ import torch.nn as nn
 
 from . import ops
 from . import engine as engine_mod
-from .engine import UNetEngine, RES_LDM, _SPEC1, _SPEC3, _SPEC_UP, _PinnedWeights
+from .engine import UNetEngine, RES_LDM, _SPEC1, _SPEC3, _SPEC_UP
+from .model_base import EngineModel
 
 _SPEC_DOWN = ops.ConvSpec(3, 2, 1, 0)
 
@@ -136,7 +137,7 @@ class Upsample(nn.Module):
         self.conv = nn.Conv2d(channels, channels, 3, padding=1)
 
 
-class UNetModel(nn.Module):
+class UNetModel(EngineModel):
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), num_heads=1, use_spatial_transformer=True, transformer_depth=1,
                  context_dim=None, num_head_channels=-1):
@@ -183,29 +184,11 @@ class UNetModel(nn.Module):
         self.out = nn.Sequential(nn.GroupNorm(32, model_channels), nn.SiLU(), nn.Conv2d(model_channels, out_channels, 3, padding=1))
         self._engine = None
 
-    def __getstate__(self):
-        """Whole-module pickles (`torch.save(model, 'unet_pruned.pth')`, ddpm_prune.py:135) carry parameters and shapes
-        only: the HIP engine (packed operands, streams) is rebuilt on first use after loading."""
-        state = dict(self.__dict__)
-        state['_engine'] = None
-        return state
+    def _new_engine(self):
+        return LdmEngine(self.config)
 
-    @property
-    def device(self):
-        return self.out[2].weight.device
-
-    def engine(self):
-        if self.device.type != 'cuda':
-            raise RuntimeError('UNetModel runs on the MI355X HIP kernels only (no CPU / PyTorch fallback)')
-        if self._engine is None:
-            self._engine = LdmEngine(self.config)
-        self._engine.packs.rebind()           # in-place weight writes are invisible to the pack cache
-        self._engine.bind({n: p.detach() for n, p in self.named_parameters()}, None)
-        return self._engine
-
-    def pin_weights(self):
-        """Context manager: the weights are frozen inside the block (sampling loop, importance pass)."""
-        return _PinnedWeights(self)
+    def _anchor(self):
+        return self.out[2].weight
 
     def forward(self, x, timesteps=None, context=None, y=None, **kwargs):
         if y is not None:

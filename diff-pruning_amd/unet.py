@@ -8,43 +8,19 @@ key names, with every weight held by a real `nn.Conv2d` / `nn.Linear` / `nn.Grou
 Those layer objects are *parameter holders only*: their own `forward` is never called; all arithmetic
 runs in the HIP kernels through `UNetEngine`.  There is no PyTorch fallback.
 """
-import math
-from collections import OrderedDict
-from types import SimpleNamespace
-
 import torch
 import torch.nn as nn
 
-from .engine import UNetEngine, _PinnedWeights
+from .engine import UNetEngine
+from .model_base import BaseOutput, DiffusersModel, FrozenConfig, _Block          # whole-module pickles name unet.FrozenConfig / _Block
 
 
-class UNet2DOutput(OrderedDict):
-    """diffusers.utils.BaseOutput behaviour (unet_2d.py:28-35): `.sample`, `["sample"]`, `[0]`, `.to_tuple()`, and -- being a
-    dict -- it is flattened by `torch_pruning.utils.flatten_as_list` when the reference's tracer walks the outputs."""
+class UNet2DOutput(BaseOutput):
+    """unet_2d.py:28-35: `.sample`.  Being a dict, it is flattened by `torch_pruning.utils.flatten_as_list` when the reference's
+    tracer walks the outputs."""
 
     def __init__(self, sample=None):
-        super().__init__()
-        self['sample'] = sample
-
-    @property
-    def sample(self):
-        return OrderedDict.__getitem__(self, 'sample')
-
-    def __getitem__(self, k):
-        return OrderedDict.__getitem__(self, k) if isinstance(k, str) else self.to_tuple()[k]
-
-    def to_tuple(self):
-        return tuple(self.values())
-
-
-class FrozenConfig(dict):
-    """dict with attribute access (Diffusers' FrozenDict behaviour: `unet.config.sample_size`)."""
-
-    def __getattr__(self, name):
-        try:
-            return self[name]
-        except KeyError:
-            raise AttributeError(name) from None          # keeps copy / pickle protocol probes working
+        super().__init__(sample=sample)
 
 
 # ---- parameter-holder modules, named as in Diffusers so that state_dict keys match ----------------
@@ -63,12 +39,15 @@ class TimestepEmbedding(nn.Module):
 
 
 class ResnetBlock2D(nn.Module):
+    """resnet.py ResnetBlock2D; temb_channels=None (the autoencoders' blocks): no time_emb_proj."""
+
     def __init__(self, in_channels, out_channels, temb_channels, groups, eps, output_scale_factor=1.0):
         super().__init__()
         self.in_channels, self.out_channels, self.output_scale_factor = in_channels, out_channels, output_scale_factor
         self.norm1 = nn.GroupNorm(groups, in_channels, eps=eps, affine=True)
         self.conv1 = nn.Conv2d(in_channels, out_channels, 3, 1, 1)
-        self.time_emb_proj = nn.Linear(temb_channels, out_channels)
+        if temb_channels is not None:
+            self.time_emb_proj = nn.Linear(temb_channels, out_channels)
         self.norm2 = nn.GroupNorm(groups, out_channels, eps=eps, affine=True)
         self.dropout = nn.Dropout(0.0)
         self.conv2 = nn.Conv2d(out_channels, out_channels, 3, 1, 1)
@@ -104,10 +83,6 @@ class Upsample2D(nn.Module):
         self.conv = nn.Conv2d(channels, channels, 3, padding=1)
 
 
-class _Block(nn.Module):
-    pass
-
-
 def _attn(cfg, channels, rescale=1.0):
     hd = cfg['attention_head_dim']
     heads = channels // hd if hd is not None else 1
@@ -128,7 +103,7 @@ _DEFAULTS = dict(
     add_attention=True, class_embed_type=None, num_class_embeds=None)
 
 
-class UNet2DModel(nn.Module):
+class UNet2DModel(DiffusersModel):
     """Construction order follows unet_2d.py:84-217, so `state_dict()` key order matches the reference."""
 
     # True: the attention logits are scaled by the q width AT RUN TIME, as the original-DDPM model does (ddpm_exp/models/
@@ -137,6 +112,7 @@ class UNet2DModel(nn.Module):
     # train.load_teacher for original-DDPM checkpoints (set it yourself on a model built otherwise), carried by whole-module pickles,
     # save_pruned / load_pruned and stage_study.prune_at_stage.
     attention_scale_from_width = False
+    _transient = ('_leaf_cache', '_structure_tracing', '_hook_warned')
 
     def __init__(self, **kwargs):
         super().__init__()
@@ -227,60 +203,22 @@ class UNet2DModel(nn.Module):
         self.dropout_seed = 0
         self._dropout_step = 0
 
-    def __getstate__(self):
-        """Whole-module pickles (`torch.save(model, 'unet_pruned.pth')`, ddpm_prune.py:135) carry parameters and shapes
-        only: the HIP engine (packed operands, streams) is rebuilt on first use after loading."""
-        state = dict(self.__dict__)
-        state['_engine'] = None
-        for k in ('_leaf_cache', '_structure_tracing', '_hook_warned'):
-            state.pop(k, None)
-        return state
+    def _new_engine(self):
+        return UNetEngine(self.config)
 
-    # ------------------------------------------------------------------------------------------
-    @property
-    def dtype(self):
-        return self.conv_in.weight.dtype
-
-    @property
-    def device(self):
-        return self.conv_in.weight.device
-
-    @classmethod
-    def from_config(cls, config):
-        return cls(**{k: v for k, v in dict(config).items() if not k.startswith('_')})
-
-    @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, **kwargs):
-        """config.json + diffusion_pytorch_model.{safetensors,bin} in a local directory (modeling_utils.py layout)."""
-        from . import checkpoint
-        return checkpoint.load_unet(pretrained_model_name_or_path, subfolder)
-
-    def save_pretrained(self, save_directory, safe_serialization=False):
-        from . import checkpoint
-        checkpoint.save_unet(self, save_directory, safe_serialization)
+    def _anchor(self):
+        return self.conv_in.weight
 
     def engine(self):
-        """The HIP execution engine bound to the *current* parameter tensors (re-bound after pruning)."""
-        if self.conv_in.weight.device.type != 'cuda':
-            raise RuntimeError('UNet2DModel runs on the MI355X HIP kernels only: move the model to a cuda device '
-                               '(there is no CPU / PyTorch fallback)')
-        if self._engine is None:
-            self._engine = UNetEngine(self.config)
-        params = {n: p.detach() for n, p in self.named_parameters()}
-        self._engine.packs.rebind()           # in-place weight writes (EMAModel.copy_to / restore) are invisible to the cache
-        self._engine.scale_from_q_width = bool(self.attention_scale_from_width)
-        self._engine.bind(params, None)
-        self._engine.set_dropout(self.dropout_table() if self.training else None, getattr(self, 'dropout_seed', 0),
-                                 getattr(self, '_dropout_step', 0))
-        return self._engine
+        eng = super().engine()
+        eng.scale_from_q_width = bool(self.attention_scale_from_width)
+        eng.set_dropout(self.dropout_table() if self.training else None, getattr(self, 'dropout_seed', 0),
+                        getattr(self, '_dropout_step', 0))
+        return eng
 
     def dropout_table(self):
         """{module name: p} of the nn.Dropout holders with p > 0 (what utils.set_dropout, utils.py:26-29, has set)."""
         return {n: float(m.p) for n, m in self.named_modules() if isinstance(m, nn.Dropout) and m.p > 0}
-
-    def pin_weights(self):
-        """Context manager: the weights are frozen inside the block (sweep, sampling loop) -> keep the packed operands."""
-        return _PinnedWeights(self)
 
     def sampling_forward(self, shape, n_calls, replay=None):
         """The no-grad forward of a sampling loop (pipeline_ddim.py:101-116, pipeline_ddpm.py:87-96) as a callable

@@ -16,14 +16,13 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .engine import _PinnedWeights
-from .unet import FrozenConfig
-from .vq import Decoder, DecoderOutput, Encoder, VQEngine, _Output
+from .model_base import BaseOutput
+from .vq import Decoder, DecoderOutput, Encoder, FirstStage, VQEngine, autoencoder_config
 
 _NO_FALLBACK = 'runs on the MI355X HIP kernels only (no CPU / PyTorch fallback)'
 
 
-class AutoencoderKLOutput(_Output):
+class AutoencoderKLOutput(BaseOutput):
     """autoencoder_kl.py:27-31: `.latent_dist`."""
 
 
@@ -136,28 +135,13 @@ _DEFAULTS = dict(in_channels=3, out_channels=3, down_block_types=('DownEncoderBl
                  scaling_factor=0.18215)
 
 
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(FirstStage):
     """Construction order follows autoencoder_kl.py:86-111, so `state_dict()` key order matches the reference."""
 
     def __init__(self, norm_type='group', **kwargs):
         super().__init__()
-        cfg = dict(_DEFAULTS)
-        unknown = set(kwargs) - set(cfg)
-        if unknown:
-            raise TypeError('unexpected AutoencoderKL arguments: %s' % sorted(unknown))
-        cfg.update(kwargs)
-        for k in ('down_block_types', 'up_block_types', 'block_out_channels'):
-            cfg[k] = tuple(cfg[k])
-        if norm_type != 'group':
-            raise NotImplementedError('AutoencoderKL: norm_type=%r (only the GroupNorm decoder is implemented)' % (norm_type,))
-        if cfg['act_fn'] not in ('silu', 'swish'):
-            raise NotImplementedError('AutoencoderKL: act_fn=%r (only silu)' % (cfg['act_fn'],))
+        cfg = self.config = autoencoder_config('AutoencoderKL', _DEFAULTS, norm_type, kwargs)
         nb = len(cfg['block_out_channels'])
-        if len(cfg['down_block_types']) != nb or len(cfg['up_block_types']) != nb:
-            raise ValueError('down_block_types, up_block_types and block_out_channels must have equal lengths')
-        if set(cfg['down_block_types']) != {'DownEncoderBlock2D'} or set(cfg['up_block_types']) != {'UpDecoderBlock2D'}:
-            raise NotImplementedError('AutoencoderKL: only DownEncoderBlock2D / UpDecoderBlock2D levels are implemented')
-        self.config = FrozenConfig(cfg)
         G, L, boc, Z = cfg['norm_num_groups'], cfg['layers_per_block'], cfg['block_out_channels'], cfg['latent_channels']
         self.encoder = Encoder(cfg['in_channels'], 2 * Z, boc, L, G)                 # double_z
         self.decoder = Decoder(Z, cfg['out_channels'], boc, L, G)
@@ -173,49 +157,8 @@ class AutoencoderKL(nn.Module):
         self.tile_overlap_factor = 0.25
         self._engine = None
 
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state['_engine'] = None
-        return state
-
-    @property
-    def dtype(self):
-        return self.quant_conv.weight.dtype
-
-    @property
-    def device(self):
-        return self.quant_conv.weight.device
-
-    @classmethod
-    def from_config(cls, config):
-        return cls(**{k: v for k, v in dict(config).items() if not k.startswith('_')})
-
-    @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, **kwargs):
-        """config.json + diffusion_pytorch_model.{safetensors,bin} in a local directory, or in its `vae/` subfolder."""
-        from . import checkpoint
-        return checkpoint.load_vae(pretrained_model_name_or_path, subfolder)
-
-    def save_pretrained(self, save_directory, safe_serialization=False):
-        from . import checkpoint
-        checkpoint.save_vae(self, save_directory, safe_serialization)
-
-    def engine(self):
-        """The HIP engine bound to the current parameters (see VQModel.engine)."""
-        if self.device.type != 'cuda':
-            raise RuntimeError('AutoencoderKL runs on the MI355X HIP kernels only: move the model to a cuda device '
-                               '(there is no CPU / PyTorch fallback)')
-        if self.dtype != torch.float32:
-            raise NotImplementedError('AutoencoderKL runs in fp32 only')
-        if self._engine is None:
-            self._engine = KLEngine(self.config)
-        self._engine.packs.rebind()
-        self._engine.bind({n: p.detach() for n, p in self.named_parameters()}, None)
-        return self._engine
-
-    def pin_weights(self):
-        """Context manager: the weights are not written inside the block -> the packed operands are kept across calls."""
-        return _PinnedWeights(self)
+    def _new_engine(self):
+        return KLEngine(self.config)
 
     def enable_tiling(self, use_tiling=True):
         self.use_tiling = use_tiling
@@ -228,10 +171,6 @@ class AutoencoderKL(nn.Module):
 
     def disable_slicing(self):
         self.use_slicing = False
-
-    @staticmethod
-    def _input(x):
-        return x.detach().to(torch.float32).contiguous()
 
     # ---- encode
     @torch.no_grad()

@@ -7,72 +7,38 @@ arguments, `.config`, `encode` / `decode` / `forward` / `quantize`, and the exac
 nn.Conv2d / nn.GroupNorm / nn.Linear / nn.Embedding (parameter holders: all arithmetic runs in the HIP kernels through
 `VQEngine`).  Forward only, fp32, no grad; there is no CPU / PyTorch fallback.
 """
-from collections import OrderedDict
-
 import torch
 import torch.nn as nn
 
 from . import ops
-from .engine import UNetEngine, _PinnedWeights, _SPEC1, _SPEC3
-from .unet import Attention, Downsample2D, FrozenConfig, Upsample2D
+from .engine import UNetEngine, _SPEC1, _SPEC3
+from .model_base import BaseOutput, DiffusersModel, FrozenConfig, _Block
+from .unet import Attention, Downsample2D, ResnetBlock2D, Upsample2D
 
 _SPEC_DOWN = ops.ConvSpec(3, 2, 0, 0)        # Downsample2D(padding=0): F.pad(0, 1, 0, 1) + stride-2 valid conv (resnet.py:196-201)
 BETA = 0.25                                 # vq_model.py:102
+_Output = BaseOutput                        # the name whole-module pickles and earlier callers know
 
 
-class _Output(OrderedDict):
-    """diffusers.utils.BaseOutput behaviour: attribute, key and index access, `.to_tuple()`."""
-
-    def __init__(self, **fields):
-        super().__init__()
-        for k, v in fields.items():
-            self[k] = v
-
-    def __getattr__(self, name):
-        try:
-            return OrderedDict.__getitem__(self, name)
-        except KeyError:
-            raise AttributeError(name) from None
-
-    def __getitem__(self, k):
-        return OrderedDict.__getitem__(self, k) if isinstance(k, str) else self.to_tuple()[k]
-
-    def to_tuple(self):
-        return tuple(self.values())
-
-
-class VQEncoderOutput(_Output):
+class VQEncoderOutput(BaseOutput):
     """vq_model.py:27-35: `.latents`."""
 
 
-class DecoderOutput(_Output):
+class DecoderOutput(BaseOutput):
     """vae.py:26-35: `.sample`."""
 
 
 # ---- parameter holders, named and ordered as in Diffusers -------------------------------------------------------
-class ResnetBlock2D(nn.Module):
-    """resnet.py ResnetBlock2D with temb_channels=None: no time_emb_proj."""
-
-    def __init__(self, in_channels, out_channels, groups, eps=1e-6):
-        super().__init__()
-        self.in_channels, self.out_channels, self.output_scale_factor = in_channels, out_channels, 1.0
-        self.norm1 = nn.GroupNorm(groups, in_channels, eps=eps, affine=True)
-        self.conv1 = nn.Conv2d(in_channels, out_channels, 3, 1, 1)
-        self.norm2 = nn.GroupNorm(groups, out_channels, eps=eps, affine=True)
-        self.dropout = nn.Dropout(0.0)
-        self.conv2 = nn.Conv2d(out_channels, out_channels, 3, 1, 1)
-        self.conv_shortcut = nn.Conv2d(in_channels, out_channels, 1, 1, 0) if in_channels != out_channels else None
-
-
-class _Block(nn.Module):
-    pass
+def _resnet(in_channels, out_channels, groups):
+    """unet.ResnetBlock2D without a time embedding, GroupNorm eps 1e-6."""
+    return ResnetBlock2D(in_channels, out_channels, None, groups, 1e-6)
 
 
 def _mid_block(channels, groups):
     """UNetMidBlock2D (unet_2d_blocks.py:392-470) as Encoder / Decoder build it: one head of `channels`, rescale 1."""
     mid = _Block()
     mid.attentions = nn.ModuleList([Attention(channels, 1, channels, groups, 1e-6, 1.0)])
-    mid.resnets = nn.ModuleList([ResnetBlock2D(channels, channels, groups), ResnetBlock2D(channels, channels, groups)])
+    mid.resnets = nn.ModuleList([_resnet(channels, channels, groups), _resnet(channels, channels, groups)])
     return mid
 
 
@@ -86,7 +52,7 @@ class Encoder(nn.Module):
         for i in range(len(boc)):
             in_c, out_c = out_c, boc[i]
             blk = _Block()
-            blk.resnets = nn.ModuleList([ResnetBlock2D(in_c if j == 0 else out_c, out_c, groups) for j in range(layers_per_block)])
+            blk.resnets = nn.ModuleList([_resnet(in_c if j == 0 else out_c, out_c, groups) for j in range(layers_per_block)])
             blk.downsamplers = nn.ModuleList([Downsample2D(out_c, 0)]) if i != len(boc) - 1 else None
             self.down_blocks.append(blk)
         self.mid_block = _mid_block(boc[-1], groups)
@@ -106,7 +72,7 @@ class Decoder(nn.Module):
         for i in range(len(rev)):
             prev, out_c = out_c, rev[i]
             blk = _Block()
-            blk.resnets = nn.ModuleList([ResnetBlock2D(prev if j == 0 else out_c, out_c, groups) for j in range(layers_per_block + 1)])
+            blk.resnets = nn.ModuleList([_resnet(prev if j == 0 else out_c, out_c, groups) for j in range(layers_per_block + 1)])
             blk.upsamplers = nn.ModuleList([Upsample2D(out_c)]) if i != len(rev) - 1 else None
             self.up_blocks.append(blk)
         self.mid_block = _mid_block(boc[-1], groups)
@@ -138,34 +104,54 @@ _DEFAULTS = dict(in_channels=3, out_channels=3, down_block_types=('DownEncoderBl
                  num_vq_embeddings=256, norm_num_groups=32, vq_embed_dim=None, scaling_factor=0.18215)
 
 
-class VQModel(nn.Module):
+def autoencoder_config(name, defaults, norm_type, kwargs):
+    """The constructor checks VQModel and AutoencoderKL share, worded with the class's `name`: the FrozenConfig of `defaults`
+    updated by `kwargs`, or the refusal."""
+    cfg = dict(defaults)
+    unknown = set(kwargs) - set(cfg)
+    if unknown:
+        raise TypeError('unexpected %s arguments: %s' % (name, sorted(unknown)))
+    cfg.update(kwargs)
+    for k in ('down_block_types', 'up_block_types', 'block_out_channels'):
+        cfg[k] = tuple(cfg[k])
+    if norm_type != 'group':
+        raise NotImplementedError('%s: norm_type=%r (only the GroupNorm decoder is implemented)' % (name, norm_type))
+    if cfg['act_fn'] not in ('silu', 'swish'):
+        raise NotImplementedError('%s: act_fn=%r (only silu)' % (name, cfg['act_fn']))
+    nb = len(cfg['block_out_channels'])
+    if len(cfg['down_block_types']) != nb or len(cfg['up_block_types']) != nb:
+        raise ValueError('down_block_types, up_block_types and block_out_channels must have equal lengths')
+    if set(cfg['down_block_types']) != {'DownEncoderBlock2D'} or set(cfg['up_block_types']) != {'UpDecoderBlock2D'}:
+        raise NotImplementedError('%s: only DownEncoderBlock2D / UpDecoderBlock2D levels are implemented' % name)
+    return FrozenConfig(cfg)
+
+
+class FirstStage(DiffusersModel):
+    """What VQModel and AutoencoderKL share besides their holders: fp32 only, `device` / `dtype` read from quant_conv."""
+
+    _fp32_only = True
+
+    def _anchor(self):
+        return self.quant_conv.weight
+
+    @staticmethod
+    def _input(x):
+        return x.detach().to(torch.float32).contiguous()
+
+
+class VQModel(FirstStage):
     """Construction order follows vq_model.py:86-115, so `state_dict()` key order matches the reference."""
 
     def __init__(self, norm_type='group', remap=None, **kwargs):
         super().__init__()
-        cfg = dict(_DEFAULTS)
-        unknown = set(kwargs) - set(cfg)
-        if unknown:
-            raise TypeError('unexpected VQModel arguments: %s' % sorted(unknown))
-        cfg.update(kwargs)
-        for k in ('down_block_types', 'up_block_types', 'block_out_channels'):
-            cfg[k] = tuple(cfg[k])
-        if norm_type != 'group':
-            raise NotImplementedError('VQModel: norm_type=%r (only the GroupNorm decoder is implemented)' % (norm_type,))
+        cfg = autoencoder_config('VQModel', _DEFAULTS, norm_type, kwargs)
         if remap is not None:
             raise NotImplementedError('VQModel: a remapped codebook (remap=...) is not implemented')
-        if cfg['act_fn'] not in ('silu', 'swish'):
-            raise NotImplementedError('VQModel: act_fn=%r (only silu)' % (cfg['act_fn'],))
-        nb = len(cfg['block_out_channels'])
-        if len(cfg['down_block_types']) != nb or len(cfg['up_block_types']) != nb:
-            raise ValueError('down_block_types, up_block_types and block_out_channels must have equal lengths')
-        if set(cfg['down_block_types']) != {'DownEncoderBlock2D'} or set(cfg['up_block_types']) != {'UpDecoderBlock2D'}:
-            raise NotImplementedError('VQModel: only DownEncoderBlock2D / UpDecoderBlock2D levels are implemented')
         D = cfg['vq_embed_dim'] if cfg['vq_embed_dim'] is not None else cfg['latent_channels']
         if D > ops.VQ_MAX_DIM:
             raise NotImplementedError('VQModel: codebook vectors of %d channels (the HIP quantizer takes at most %d)'
                                       % (D, ops.VQ_MAX_DIM))
-        self.config = FrozenConfig(cfg)
+        self.config = cfg
         G, L, boc = cfg['norm_num_groups'], cfg['layers_per_block'], cfg['block_out_channels']
         self.encoder = Encoder(cfg['in_channels'], cfg['latent_channels'], boc, L, G)
         self.quant_conv = nn.Conv2d(cfg['latent_channels'], D, 1)
@@ -174,54 +160,8 @@ class VQModel(nn.Module):
         self.decoder = Decoder(cfg['latent_channels'], cfg['out_channels'], boc, L, G)
         self._engine = None
 
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state['_engine'] = None
-        return state
-
-    @property
-    def dtype(self):
-        return self.quant_conv.weight.dtype
-
-    @property
-    def device(self):
-        return self.quant_conv.weight.device
-
-    @classmethod
-    def from_config(cls, config):
-        return cls(**{k: v for k, v in dict(config).items() if not k.startswith('_')})
-
-    @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, **kwargs):
-        """config.json + diffusion_pytorch_model.{safetensors,bin} in a local directory (modeling_utils.py layout)."""
-        from . import checkpoint
-        return checkpoint.load_vq(pretrained_model_name_or_path, subfolder)
-
-    def save_pretrained(self, save_directory, safe_serialization=False):
-        from . import checkpoint
-        checkpoint.save_vq(self, save_directory, safe_serialization)
-
-    def engine(self):
-        """The HIP engine bound to the current parameters.  In-place weight writes are invisible to the packed-operand cache, so it
-        is dropped on every call outside `pin_weights()` (the weights are packed again)."""
-        if self.device.type != 'cuda':
-            raise RuntimeError('VQModel runs on the MI355X HIP kernels only: move the model to a cuda device '
-                               '(there is no CPU / PyTorch fallback)')
-        if self.dtype != torch.float32:
-            raise NotImplementedError('VQModel runs in fp32 only')
-        if self._engine is None:
-            self._engine = VQEngine(self.config)
-        self._engine.packs.rebind()
-        self._engine.bind({n: p.detach() for n, p in self.named_parameters()}, None)
-        return self._engine
-
-    def pin_weights(self):
-        """Context manager: the weights are not written inside the block -> the packed operands are kept across calls."""
-        return _PinnedWeights(self)
-
-    @staticmethod
-    def _input(x):
-        return x.detach().to(torch.float32).contiguous()
+    def _new_engine(self):
+        return VQEngine(self.config)
 
     @torch.no_grad()
     def encode(self, x, return_dict=True):
