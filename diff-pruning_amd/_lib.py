@@ -113,6 +113,10 @@ class DpmSolverCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sigma_s', 'alpha_s', 'kx', 'k0', 'k1', 'k2', 'ir0', 'ir1', 'q', 'iq')]
 
 
+class PndmCoef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'sc', 'd', 'den', 'c6', 'c3', 'c24')]
+
+
 class X0Coef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'range', 'c0', 'c1', 'cz')]
 
@@ -214,6 +218,7 @@ SIGNATURES = {
     'dp_cfg_denoise_step': [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _ll, _vp],
     'dp_dpm_solver_step': [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(DpmSolverCoef), _vp, _vp, _ll, _vp],
     'dp_unipc_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(UniPCCoef), _vp, _vp, _vp, _ll, _vp],
+    'dp_pndm_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(PndmCoef), _vp, _vp, _ll, _vp],
     'dp_x0_abs_quantile_workspace': [_ll, _ll],
     'dp_x0_abs_quantile': [_vp, _vp, _ll, _ll, _i, _f, _f, _ll, _ll, _f, _f, _i, _vp, _vp, _vp],
     'dp_x0_step': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(X0Coef), _vp, _vp, _ll, _ll, _vp],

@@ -7,6 +7,8 @@
   DDPMScheduler.set_timesteps  scheduling_ddpm.py:185-236
   DDPMScheduler.step           scheduling_ddpm.py:312-406   (HIP kernel dp_ddpm_step; epsilon prediction)
   DDPMPipeline.__call__        pipelines/ddpm/pipeline_ddpm.py:24-105 (ancestral sampling loop)
+  PNDMScheduler.step           scheduling_pndm.py:192-399   (HIP kernel dp_pndm_step)
+  PNDMPipeline.__call__        pipelines/pndm/pipeline_pndm.py:47-99
   randn_tensor                 utils/torch_utils.py:36-77   (CPU-generator semantics kept for seed parity)
 Host-side table arithmetic (1000-entry alpha-bar table) is fp32 torch on the CPU, exactly as in the reference.
 """
@@ -713,6 +715,158 @@ class UniPCMultistepScheduler(_MultistepBase):
         return SchedulerOutput(prev_sample=prev)
 
 
+class PNDMScheduler(_SchedulerBase):
+    """scheduling_pndm.py:58-427, F-PNDM: twelve Runge-Kutta calls (step_prk) and then the linear multistep method (step_plms), or
+    the multistep method alone (`skip_prk_steps`), for epsilon and `v_prediction` models.  The counter logic is the reference's, its
+    oddities included: the Runge-Kutta stages 1 .. 3 start from `cur_sample`, not from the `sample` they are handed; the second call
+    with `skip_prk_steps` shifts its timesteps and goes back to `cur_sample`; a negative previous timestep selects
+    `final_alpha_cumprod`.  The scalars of a step are 0-d fp32 torch arithmetic on the CPU in the reference's operation order, each
+    `** 0.5` correctly rounded (_rounded_once: the reference's bits on a host whose math library rounds sqrt correctly, and the same
+    bits on every host); the per-element work -- the accumulation or the multistep combination, the v-conversion and formula (9) --
+    is ONE launch of dp_pndm_step (ops.pndm_step).  The timesteps are kept as host lists beside the `timesteps` tensor, so `step`
+    reads nothing back from the device.  The history `ets` is a ring of four device buffers that the steps write in turn (the model's
+    own tensor is not kept: a captured forward reuses its output buffer); `cur_sample` is held by reference, as the reference holds it.
+    Not carried: `trained_betas` (NotImplementedError); `sample`-prediction models (ValueError in `step`, as in the reference);
+    models that predict a variance (NotImplementedError)."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'skip_prk_steps',
+                    'set_alpha_to_one', 'prediction_type', 'steps_offset')
+    order = 1
+    pndm_order = 4
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', trained_betas=None,
+                 skip_prk_steps=False, set_alpha_to_one=False, prediction_type='epsilon', steps_offset=0):
+        if trained_betas is not None:
+            raise NotImplementedError('trained_betas is not on the hot path')
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, trained_betas=trained_betas, skip_prk_steps=skip_prk_steps,
+                                      set_alpha_to_one=set_alpha_to_one, prediction_type=prediction_type, steps_offset=steps_offset)
+        self._init_tables(num_train_timesteps, beta_start, beta_end, beta_schedule,
+                          _betas_for_alpha_bar(num_train_timesteps) if beta_schedule == 'squaredcos_cap_v2' else None)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self.num_inference_steps = None
+        self._timesteps = np.arange(0, num_train_timesteps)[::-1].copy()
+        self.prk_timesteps = self.plms_timesteps = self.timesteps = None
+        self._reset()
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+    def _reset(self):
+        self.counter = 0
+        self.cur_sample = None
+        self.ets = []                                 # the history: up to four buffers of this scheduler's own, newest last
+        self._acc = None                              # cur_model_output, the Runge-Kutta accumulator: written by stage 0, read by 1 .. 3
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """:152-190 with the reference's numpy expressions, repeats included; the running values reset."""
+        T = self.config.num_train_timesteps
+        if not self.config.skip_prk_steps and num_inference_steps < self.pndm_order:
+            raise ValueError('num_inference_steps = %d: without skip_prk_steps the Runge-Kutta timesteps need at least %d inference '
+                             'steps (the reference fails to broadcast its arrays there)' % (num_inference_steps, self.pndm_order))
+        self.num_inference_steps = num_inference_steps
+        step_ratio = T // num_inference_steps
+        self._timesteps = (np.arange(0, num_inference_steps) * step_ratio).round()
+        self._timesteps += self.config.steps_offset
+        if self.config.skip_prk_steps:
+            self.prk_timesteps = np.array([])
+            self.plms_timesteps = np.concatenate([self._timesteps[:-1], self._timesteps[-2:-1], self._timesteps[-1:]])[::-1].copy()
+        else:
+            prk = np.array(self._timesteps[-self.pndm_order:]).repeat(2) + np.tile(
+                np.array([0, T // num_inference_steps // 2]), self.pndm_order)
+            self.prk_timesteps = (prk[:-1].repeat(2)[1:-1])[::-1].copy()
+            self.plms_timesteps = self._timesteps[:-3][::-1].copy()
+        ts = np.concatenate([self.prk_timesteps, self.plms_timesteps]).astype(np.int64)
+        self.timesteps = torch.from_numpy(ts).to(device)
+        self._ts = [int(v) for v in ts]                               # the host's copies: what `step` looks timesteps up in
+        self._prk = [int(v) for v in self.prk_timesteps]
+        self._reset()
+
+    def step_coefs(self, timestep, prev_timestep):
+        """The fp32 scalars of _get_prev_sample (:371-397) as ops.pndm_step names them: sa = alpha_prod_t ** 0.5 and
+        sb = beta_prod_t ** 0.5 (the v-conversion; v_prediction only), sc = sample_coeff, d = alpha_prod_t_prev - alpha_prod_t,
+        den = model_output_denom_coeff."""
+        pt = self.config.prediction_type
+        if pt not in ('epsilon', 'v_prediction'):
+            raise ValueError('prediction_type given as %s must be one of `epsilon` or `v_prediction`' % pt)
+
+        def sqrt(v):
+            return _rounded_once(torch.sqrt, v)
+        alpha_prod_t = self.alphas_cumprod[timestep]
+        alpha_prod_t_prev = self.alphas_cumprod[prev_timestep] if prev_timestep >= 0 else self.final_alpha_cumprod
+        beta_prod_t = 1 - alpha_prod_t
+        beta_prod_t_prev = 1 - alpha_prod_t_prev
+        c = {}
+        if pt == 'v_prediction':
+            c['sa'], c['sb'] = sqrt(alpha_prod_t), sqrt(beta_prod_t)
+        c['sc'] = sqrt(alpha_prod_t_prev / alpha_prod_t)
+        c['den'] = alpha_prod_t * sqrt(beta_prod_t_prev) + sqrt(alpha_prod_t * beta_prod_t * alpha_prod_t_prev)
+        c['d'] = alpha_prod_t_prev - alpha_prod_t
+        return {k: float(v) for k, v in c.items()}
+
+    def _fits(self, buf, sample):
+        return buf is not None and buf.shape == sample.shape and buf.device == sample.device
+
+    def step(self, model_output, timestep, sample, return_dict=True, out=None):
+        """:192-343: step_prk while the counter is inside prk_timesteps (and the Runge-Kutta calls are not skipped), step_plms after
+        that; exactly one launch, nothing read back.  `out` (extension): the buffer that takes prev_sample, which may be `sample`
+        itself; without it a step writes none of its inputs."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if model_output.shape[1] != sample.shape[1]:
+            raise NotImplementedError('learned-variance models are not part of this path')
+        cfg = self.config
+        if cfg.prediction_type not in ('epsilon', 'v_prediction'):
+            raise ValueError('prediction_type given as %s must be one of `epsilon` or `v_prediction`' % cfg.prediction_type)
+        t = int(timestep)
+        stride = cfg.num_train_timesteps // self.num_inference_steps
+        acc, hist, hist_out = None, (), None
+        if self.counter < len(self._prk) and not cfg.skip_prk_steps:                                  # step_prk, :251-270
+            prev_t = t - (0 if self.counter % 2 else stride // 2)
+            t = self._prk[self.counter // 4 * 4]
+            mode = ops.PNDM_PRK0 + self.counter % 4
+            if mode == ops.PNDM_PRK0:
+                if not self._fits(self._acc, sample):
+                    self._acc = torch.empty_like(sample, memory_format=torch.contiguous_format)
+                hist_out = torch.empty_like(sample, memory_format=torch.contiguous_format)
+                self.cur_sample = sample
+            acc = self._acc
+            x = self.cur_sample if self.cur_sample is not None else sample
+            keep = self.ets
+        else:                                                                                         # step_plms, :306-337
+            if not cfg.skip_prk_steps and len(self.ets) < 3:
+                raise ValueError('%s can only be run AFTER scheduler has been run in \'prk\' mode for at least 12 iterations'
+                                 % type(self).__name__)
+            prev_t = t - stride
+            x = sample
+            if self.counter != 1:
+                keep = self.ets[-3:]
+                old = self.ets[:-3]
+                hist_out = old[0] if old and self._fits(old[0], sample) else torch.empty_like(sample, memory_format=torch.contiguous_format)
+                if keep:
+                    mode = (ops.PNDM_PLMS2, ops.PNDM_PLMS3, ops.PNDM_PLMS4)[len(keep) - 1]
+                elif self.counter == 0:
+                    mode = ops.PNDM_PLMS1
+                    self.cur_sample = sample
+                else:
+                    raise RuntimeError('step_plms without history at counter %d: not a state that `step` reaches' % self.counter)
+            else:
+                if len(self.ets) != 1:
+                    raise RuntimeError('step_plms at counter 1 with %d history entries: not a state that `step` reaches' % len(self.ets))
+                prev_t, t = t, t + stride                                                             # :319-321
+                keep = self.ets
+                mode = ops.PNDM_PLMS_AVG
+                x = self.cur_sample
+                self.cur_sample = None
+            hist = keep[::-1]
+        prev, appended = ops.pndm_step(x.contiguous(), model_output.contiguous(), self.step_coefs(t, prev_t), mode,
+                                       v_pred=cfg.prediction_type == 'v_prediction', acc=acc, hist=hist, out=out, hist_out=hist_out)
+        self.ets = keep + [appended] if appended is not None else keep
+        self.counter += 1                             # (cur_model_output = 0 after stage 3: stage 0 of the next round overwrites _acc)
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
 @dataclass
 class ImagePipelineOutput:
     images: object
@@ -836,6 +990,29 @@ class DDIMPipeline(_PipelineBase):
             for t in self.progress_bar(ts):
                 model_output = fwd(image, t)
                 image = self.scheduler.step(model_output, t, image, eta=eta, generator=generator, **extra).prev_sample
+        finally:
+            fwd.close()
+        return _to_output(self, image, output_type, return_dict)
+
+
+class PNDMPipeline(_PipelineBase):
+    """pipelines/pndm/pipeline_pndm.py:26-99: one UNet forward + one dp_pndm_step per entry of the scheduler's timestep list, which
+    is longer than `num_inference_steps` (the Runge-Kutta calls, the repeated timestep of `skip_prk_steps`)."""
+
+    def __init__(self, unet, scheduler):
+        super().__init__(unet, PNDMScheduler.from_config(scheduler.config))                      # pipeline_pndm.py:43
+
+    @torch.no_grad()
+    def __call__(self, batch_size=1, num_inference_steps=50, generator=None, output_type='pil', return_dict=True, **kwargs):
+        shape = _image_shape(self.unet, batch_size)
+        image = randn_tensor(shape, generator=generator, device=self.device)
+        self.scheduler.set_timesteps(num_inference_steps)
+        ts = self.scheduler._ts                                               # the host's list: nothing is read back
+        fwd = _sampling_forward(self.unet, shape, len(ts))
+        try:
+            for t in self.progress_bar(ts):
+                model_output = fwd(image, t)
+                image = self.scheduler.step(model_output, t, image).prev_sample
         finally:
             fwd.close()
         return _to_output(self, image, output_type, return_dict)

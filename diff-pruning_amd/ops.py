@@ -2165,7 +2165,60 @@ def dpm_solver_step(x, e, coef, order=1, data_pred=True, m1=None, m2=None, out=N
     return out, m0_out
 
 
-UNIPC_MAX_BLOCKS = 4096              # DP_UNIPC_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
+PNDM_MAX_BLOCKS = 4096               # DP_PNDM_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
+PNDM_COEF = ('sa', 'sb', 'sc', 'd', 'den', 'c6', 'c3', 'c24')
+# DP_PNDM_* (include/dp_hip.h): the values of `mode`, and per mode (accumulator read, accumulator written, history entries read,
+# hist_out written)
+PNDM_PRK0, PNDM_PRK1, PNDM_PRK2, PNDM_PRK3, PNDM_PLMS1, PNDM_PLMS_AVG, PNDM_PLMS2, PNDM_PLMS3, PNDM_PLMS4 = range(9)
+PNDM_MODES = {PNDM_PRK0: (False, True, 0, True), PNDM_PRK1: (True, True, 0, False), PNDM_PRK2: (True, True, 0, False),
+              PNDM_PRK3: (True, False, 0, False), PNDM_PLMS1: (False, False, 0, True), PNDM_PLMS_AVG: (False, False, 1, False),
+              PNDM_PLMS2: (False, False, 1, True), PNDM_PLMS3: (False, False, 2, True), PNDM_PLMS4: (False, False, 3, True)}
+PNDM_FRACTIONS = dict(c6=1 / 6, c3=1 / 3, c24=1 / 24)      # Python doubles, rounded to fp32 once on the way into the struct
+
+
+def pndm_step(x, e, coef, mode, v_pred=False, acc=None, hist=(), out=None, hist_out=None):
+    """One step of the PNDM scheduler (dp_pndm_step, csrc/pndm.hip) over flat fp32 data.  `coef`: the host's fp32 scalars by name
+    (PNDM_COEF; sa / sb are read with `v_pred` only; c6 / c3 / c24 default to fp32(1/6), fp32(1/3), fp32(1/24)).  With m the mode's
+    combined output -- PRK0: e (acc = c6 e + 0); PRK1 / PRK2: e (acc += c3 e); PRK3: acc + c6 e; PLMS1: e; PLMS_AVG: (e + h1) / 2;
+    PLMS2: (3 e - h1) / 2; PLMS3: ((23 e - 16 h1) + 5 h2) / 12; PLMS4: c24 (((55 e - 59 h1) + 37 h2) - 9 h3) -- and, with `v_pred`,
+    m = sa m + sb x:  out = sc x - (d m) / den.  `acc`: the Runge-Kutta accumulator, updated in place (required in the PRK modes);
+    `hist`: the older model outputs the mode reads, newest first; `hist_out` takes a copy of e in the modes that append it (PRK0,
+    PLMS1 .. PLMS4 but not PLMS_AVG) and is ignored in the others.  `out` may be `x`; `hist_out` may be one of `hist` (the oldest
+    buffer of the caller's ring); no other buffer may be shared.  Returns (out, hist_out), hist_out None where nothing was appended."""
+    n = x.numel()
+    assert mode in PNDM_MODES, mode
+    reads_acc, writes_acc, need, appends = PNDM_MODES[mode]
+    assert x.dtype == _f32 and e.dtype == _f32 and x.is_contiguous() and e.is_contiguous() and e.numel() == n
+    hist = list(hist)[:need]
+    assert len(hist) == need and all(h is not None and h.dtype == _f32 and h.is_contiguous() and h.numel() == n for h in hist), \
+        'pndm_step: history below the mode'
+    if reads_acc or writes_acc:
+        assert acc is not None and acc.dtype == _f32 and acc.is_contiguous() and acc.numel() == n, 'pndm_step: a PRK mode without acc'
+    else:
+        acc = None
+    if out is None:
+        out = torch.empty_like(x)
+    if not appends:
+        hist_out = None
+    elif hist_out is None:
+        hist_out = torch.empty_like(x)
+    outs = [o for o in (out, acc, hist_out) if o is not None]
+    for o in outs:
+        assert o.dtype == _f32 and o.is_contiguous() and o.numel() == n
+    assert len({o.data_ptr() for o in outs}) == len(outs)
+    assert out.data_ptr() not in [e.data_ptr()] + [h.data_ptr() for h in hist]
+    assert acc is None or acc.data_ptr() not in [x.data_ptr(), e.data_ptr()] + [h.data_ptr() for h in hist]
+    assert hist_out is None or hist_out.data_ptr() not in (x.data_ptr(), e.data_ptr())
+    unknown = set(coef) - set(PNDM_COEF)
+    assert not unknown, unknown
+    c = L.PndmCoef(**{k: float(v) for k, v in dict(PNDM_FRACTIONS, **coef).items()})
+    h = [_p(t) for t in hist] + [None] * (3 - need)
+    L.check(_lib().dp_pndm_step(_p(x), _p(e), _p(acc), h[0], h[1], h[2], int(mode), 1 if v_pred else 0, C.byref(c), _p(out),
+                                _p(hist_out), n, _stream()), 'dp_pndm_step')
+    return out, hist_out
+
+
+UNIPC_MAX_BLOCKS = 4096             # DP_UNIPC_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
 UNIPC_COEF = ('sigma_s', 'alpha_s', 'c_cx', 'c_c0', 'c_cB', 'c_rk1', 'c_rk2', 'c_rho1', 'c_rho2', 'c_rho_last',
               'p_cx', 'p_c0', 'p_cB', 'p_rk1', 'p_rk2', 'p_rho1', 'p_rho2')
 

@@ -523,7 +523,7 @@ int dp_ddpm_step(const float* x, const float* eps, const float* vnoise, float sq
                  float c_xt, float sigma, int clip, float clip_range, float* out, long long n, void* stream);
 
 /* ---- The head / body / tail access rule of the elementwise step launchers below (dp_denoise_step, dp_cfg_denoise_step,
- * dp_dpm_solver_step, dp_unipc_step, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
+ * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
  * When every pointer in use (a NULL or unread one does not count) shares one 4-byte-aligned phase modulo 16, a scalar head of
  * 0 .. 3 elements brings all of them to 16 bytes: the n4 = (n - head) / 4 groups after it take 16-byte accesses, the head and the
  * n - head - 4 n4 tail elements 4-byte ones.  Otherwise every access is 4 bytes (head = n).  Any n: long long indexing, one lane
@@ -625,6 +625,46 @@ typedef struct dp_unipc_coef {
 int dp_unipc_step(const float* e, const float* x_pred, const float* x_last, const float* m0, const float* m1, const float* m2,
                   int pc, int pp, int predict_x0, const dp_unipc_coef* coef, float* m_new, float* x_c, float* x_next, long long n,
                   void* stream);
+
+/* One step of the PNDM scheduler (csrc/pndm.hip; diffusers/schedulers/scheduling_pndm.py:251-270 step_prk, :314-337 step_plms,
+ * :358-399 _get_prev_sample) over n fp32 elements, one pass, in the reference's operation order.  e: the model output, x: the state
+ * the update starts from (cur_sample in the Runge-Kutta stages), acc: the Runge-Kutta accumulator, h1 .. h3: older model outputs,
+ * newest first.  The combined output m of each mode, and what the mode writes beside x_next:
+ *   DP_PNDM_PRK0      m = e;  acc = c6 * e + 0;  hist_out = e        (the reference adds to a Python 0: -0 becomes +0)
+ *   DP_PNDM_PRK1/2    m = e;  acc = acc + c3 * e                     (in place)
+ *   DP_PNDM_PRK3      m = acc + c6 * e                               (acc is read only: the host forgets it)
+ *   DP_PNDM_PLMS1     m = e;  hist_out = e
+ *   DP_PNDM_PLMS_AVG  m = (e + h1) / 2                               (skip_prk_steps, the second call: e is not appended)
+ *   DP_PNDM_PLMS2     m = (3 * e - h1) / 2;  hist_out = e
+ *   DP_PNDM_PLMS3     m = ((23 * e - 16 * h1) + 5 * h2) / 12;  hist_out = e
+ *   DP_PNDM_PLMS4     m = c24 * (((55 * e - 59 * h1) + 37 * h2) - 9 * h3);  hist_out = e
+ * then, v_pred != 0:  m = sa * m + sb * x;  and always  x_next = sc * x - (d * m) / den.
+ * Every operation rounded separately, true divisions; sa .. den are the host's 0-d fp32 arithmetic on the alphas_cumprod table
+ * (sa = alpha_prod_t ** 0.5, sb = beta_prod_t ** 0.5, sc = sample_coeff, d = alpha_prod_t_prev - alpha_prod_t,
+ * den = model_output_denom_coeff), c6 / c3 / c24 the doubles 1/6, 1/3, 1/24 rounded to fp32 once.  hist_out is a copy of e: the
+ * caller's history owns its buffers.  A pointer the mode neither reads nor writes is ignored and may be NULL.
+ * Aliases: `x_next` may be `x` itself, `acc` is one buffer updated in place, and `hist_out` may be `h1`, `h2` or `h3` itself -- the
+ * oldest buffer of the caller's ring, which this very step may still read: each lane reads every input of its elements before it
+ * writes any of them, and no other lane touches them.  Any other overlap between an output and another buffer is
+ * hipErrorInvalidValue, as are a null pointer that the mode reads or writes and a mode outside 0 .. 8: nothing is launched.
+ * n <= 0 is a no-op.  Accesses: the head / body / tail rule above, at most DP_PNDM_MAX_BLOCKS blocks. */
+#define DP_PNDM_MAX_BLOCKS 4096
+#define DP_PNDM_PRK0 0
+#define DP_PNDM_PRK1 1
+#define DP_PNDM_PRK2 2
+#define DP_PNDM_PRK3 3
+#define DP_PNDM_PLMS1 4
+#define DP_PNDM_PLMS_AVG 5
+#define DP_PNDM_PLMS2 6
+#define DP_PNDM_PLMS3 7
+#define DP_PNDM_PLMS4 8
+typedef struct dp_pndm_coef {
+    float sa, sb;                       /* the v-conversion (v_pred only) */
+    float sc, d, den;                   /* formula (9) */
+    float c6, c3, c24;                  /* fp32(1/6), fp32(1/3), fp32(1/24) */
+} dp_pndm_coef;
+int dp_pndm_step(const float* x, const float* e, float* acc, const float* h1, const float* h2, const float* h3, int mode, int v_pred,
+                 const dp_pndm_coef* coef, float* x_next, float* hist_out, long long n, void* stream);
 
 /* x0 forming, dynamic thresholding and the DDPM / DDIM update for epsilon, sample and v-prediction models (csrc/threshold.hip;
  * diffusers/schedulers/scheduling_ddpm.py:278-310, :355-401, scheduling_ddim.py:205-237, :334-385) over B images of n fp32 elements.
