@@ -117,6 +117,17 @@ class PndmCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'sc', 'd', 'den', 'c6', 'c3', 'c24')]
 
 
+class RepaintCoef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'sap', 's1', 'cd', 'sd')]
+
+
+REPAINT_UNDO_MAX = 8                  # DP_REPAINT_UNDO_MAX (include/dp_hip.h)
+
+
+class RepaintUndoCoef(C.Structure):
+    _fields_ = [('z', C.c_void_p * REPAINT_UNDO_MAX), ('a', C.c_float * REPAINT_UNDO_MAX), ('b', C.c_float * REPAINT_UNDO_MAX)]
+
+
 class X0Coef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'range', 'c0', 'c1', 'cz')]
 
@@ -219,6 +230,8 @@ SIGNATURES = {
     'dp_dpm_solver_step': [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(DpmSolverCoef), _vp, _vp, _ll, _vp],
     'dp_unipc_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(UniPCCoef), _vp, _vp, _vp, _ll, _vp],
     'dp_pndm_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(PndmCoef), _vp, _vp, _ll, _vp],
+    'dp_repaint_step': [_vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _i, _i, C.POINTER(RepaintCoef), _vp, _vp, _ll, _vp],
+    'dp_repaint_undo': [_vp, C.POINTER(RepaintUndoCoef), _i, _vp, _ll, _vp],
     'dp_x0_abs_quantile_workspace': [_ll, _ll],
     'dp_x0_abs_quantile': [_vp, _vp, _ll, _ll, _i, _f, _f, _ll, _ll, _f, _f, _i, _vp, _vp, _vp],
     'dp_x0_step': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(X0Coef), _vp, _vp, _ll, _ll, _vp],

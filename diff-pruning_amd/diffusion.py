@@ -9,6 +9,8 @@
   DDPMPipeline.__call__        pipelines/ddpm/pipeline_ddpm.py:24-105 (ancestral sampling loop)
   PNDMScheduler.step           scheduling_pndm.py:192-399   (HIP kernel dp_pndm_step)
   PNDMPipeline.__call__        pipelines/pndm/pipeline_pndm.py:47-99
+  RePaintScheduler.step        scheduling_repaint.py:216-301 (HIP kernel dp_repaint_step), undo_step :303-318 (dp_repaint_undo)
+  RePaintPipeline.__call__     pipelines/repaint/pipeline_repaint.py:82-171
   randn_tensor                 utils/torch_utils.py:36-77   (CPU-generator semantics kept for seed parity)
 Host-side table arithmetic (1000-entry alpha-bar table) is fp32 torch on the CPU, exactly as in the reference.
 """
@@ -868,6 +870,148 @@ class PNDMScheduler(_SchedulerBase):
 
 
 @dataclass
+class RePaintSchedulerOutput:
+    prev_sample: torch.Tensor
+    pred_original_sample: torch.Tensor = None
+
+
+class RePaintScheduler(_SchedulerBase):
+    """scheduling_repaint.py:75-329, RePaint inpainting with an unconditional epsilon model: `step` is the DDIM update of the unknown
+    region, the re-noised original image of the known region and the blend by the mask; `undo_step` re-noises a state by
+    num_train_timesteps // num_inference_steps steps of the forward process.  The timestep list walks down and jumps back up
+    (`jump_length`, `jump_n_sample`).  The scalars are 0-d fp32 torch arithmetic on the CPU in the reference's operation order, each
+    `** 0.5` correctly rounded (_rounded_once); the per-element work of `step` is ONE launch of dp_repaint_step (ops.repaint_step) and
+    that of `undo_step` one launch of dp_repaint_undo per eight re-noising steps (ops.repaint_undo).  The timesteps are kept as a
+    host list beside the `timesteps` tensor, so neither reads anything back from the device.  The noise is drawn as the reference
+    draws it: one randn_tensor per `step`, always, and one per re-noising step.  `eta` is an attribute that the pipeline
+    overwrites, as in the reference.  Not carried: `trained_betas` and models that predict a variance (NotImplementedError)."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'eta', 'trained_betas', 'clip_sample')
+    order = 1
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', eta=0.0,
+                 trained_betas=None, clip_sample=True):
+        if trained_betas is not None:
+            raise NotImplementedError('trained_betas is not on the hot path')
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, eta=eta, trained_betas=trained_betas, clip_sample=clip_sample)
+        betas = None
+        if beta_schedule == 'squaredcos_cap_v2':
+            betas = _betas_for_alpha_bar(num_train_timesteps)
+        elif beta_schedule == 'sigmoid':                                         # :131-134, GeoDiff's schedule
+            betas = _rounded_once(torch.sigmoid, torch.linspace(-6, 6, num_train_timesteps)) * (beta_end - beta_start) + beta_start
+        self._init_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, betas)
+        self.one = torch.tensor(1.0)
+        self.final_alpha_cumprod = torch.tensor(1.0)
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
+        self._ts = [int(v) for v in self.timesteps]
+        self.eta = eta
+        self._coefs, self._mask = {}, None
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+    def set_timesteps(self, num_inference_steps, jump_length=10, jump_n_sample=10, device=None):
+        """:174-195: down one step at a time; at every `jump_length`-th step, `jump_n_sample - 1` times, back up `jump_length`
+        steps (the entries that `undo_step` serves)."""
+        num_inference_steps = min(self.config.num_train_timesteps, num_inference_steps)
+        self.num_inference_steps = num_inference_steps
+        timesteps = []
+        jumps = {}
+        for j in range(0, num_inference_steps - jump_length, jump_length):
+            jumps[j] = jump_n_sample - 1
+        t = num_inference_steps
+        while t >= 1:
+            t = t - 1
+            timesteps.append(t)
+            if jumps.get(t, 0) > 0:
+                jumps[t] = jumps[t] - 1
+                for _ in range(jump_length):
+                    t = t + 1
+                    timesteps.append(t)
+        timesteps = np.array(timesteps) * (self.config.num_train_timesteps // self.num_inference_steps)
+        self.timesteps = torch.from_numpy(timesteps).to(device)
+        self._ts = [int(v) for v in timesteps]                        # the host's copy: what the pipeline iterates over
+        self._coefs = {}
+
+    def _get_variance(self, t):
+        """:197-214."""
+        prev_timestep = t - self.config.num_train_timesteps // self.num_inference_steps
+        alpha_prod_t = self.alphas_cumprod[t]
+        alpha_prod_t_prev = self.alphas_cumprod[prev_timestep] if prev_timestep >= 0 else self.final_alpha_cumprod
+        beta_prod_t = 1 - alpha_prod_t
+        beta_prod_t_prev = 1 - alpha_prod_t_prev
+        return (beta_prod_t_prev / beta_prod_t) * (1 - alpha_prod_t / alpha_prod_t_prev)
+
+    def step_coefs(self, timestep):
+        """The fp32 scalars of `step` (:251-290) as ops.repaint_step names them: sa = alpha_prod_t ** 0.5, sb = beta_prod_t ** 0.5,
+        sap = alpha_prod_t_prev ** 0.5, s1 = (1 - alpha_prod_t_prev) ** 0.5, sd = std_dev_t = eta * variance ** 0.5,
+        cd = (1 - alpha_prod_t_prev - std_dev_t ** 2) ** 0.5.  Kept per (timestep, eta): the list revisits its timesteps."""
+        key = ('step', timestep, self.eta)
+        c = self._coefs.get(key)
+        if c is not None:
+            return c
+
+        def sqrt(v):
+            return _rounded_once(torch.sqrt, v)
+        prev_timestep = timestep - self.config.num_train_timesteps // self.num_inference_steps
+        alpha_prod_t = self.alphas_cumprod[timestep]
+        alpha_prod_t_prev = self.alphas_cumprod[prev_timestep] if prev_timestep >= 0 else self.final_alpha_cumprod
+        beta_prod_t = 1 - alpha_prod_t
+        std_dev_t = self.eta * sqrt(self._get_variance(timestep))
+        c = dict(sa=sqrt(alpha_prod_t), sb=sqrt(beta_prod_t), sap=sqrt(alpha_prod_t_prev), s1=sqrt(1 - alpha_prod_t_prev),
+                 cd=sqrt(1 - alpha_prod_t_prev - std_dev_t ** 2), sd=std_dev_t)
+        c = self._coefs[key] = {k: float(v) for k, v in c.items()}
+        return c
+
+    def undo_coefs(self, timestep):
+        """[(a_i, b_i)] of `undo_step` (:304-316): a_i = (1 - beta) ** 0.5, b_i = beta ** 0.5 at timestep + i."""
+        key = ('undo', timestep)
+        c = self._coefs.get(key)
+        if c is None:
+            n = self.config.num_train_timesteps // self.num_inference_steps
+            betas = [self.betas[timestep + i] for i in range(n)]
+            c = self._coefs[key] = [(float(_rounded_once(torch.sqrt, 1 - b)), float(_rounded_once(torch.sqrt, b))) for b in betas]
+        return c
+
+    def _mask_for(self, mask, sample):
+        """The mask as ops.repaint_step reads it: itself where the kernel indexes its shape in place, otherwise expanded to the
+        sample's shape, once per mask."""
+        if ops.repaint_mask_geometry(sample.shape, mask.shape) is not None:
+            return mask.contiguous()
+        if self._mask is None or self._mask[0] is not mask or self._mask[1].shape != sample.shape:
+            self._mask = (mask, mask.expand(sample.shape).contiguous())
+        return self._mask[1]
+
+    def step(self, model_output, timestep, sample, original_image, mask, generator=None, return_dict=True, out=None, need_x0=True):
+        """:216-301: exactly one launch, nothing read back; one randn_tensor draw per call, also where the noise is not added.
+        `out` (extension): the buffer that takes prev_sample, which may be `sample` itself; without it a step writes none of its
+        inputs.  `need_x0=False` (extension): pred_original_sample is not written and is None in the result."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if model_output.shape[1] != sample.shape[1]:
+            raise NotImplementedError('learned-variance models are not part of this path')
+        t = int(timestep)
+        noise = randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+        prev, x0 = ops.repaint_step(sample.contiguous(), model_output.contiguous(), noise, original_image.contiguous(),
+                                    self._mask_for(mask, sample), self.step_coefs(t), clip=self.config.clip_sample,
+                                    add_noise=t > 0 and self.eta > 0, out=out, x0_out=True if need_x0 else None)
+        if not return_dict:
+            return (prev, x0)
+        return RePaintSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+    def undo_step(self, sample, timestep, generator=None, out=None):
+        """:303-318: num_train_timesteps // num_inference_steps re-noising steps from `timestep`, each with a randn_tensor draw of
+        its own, in ceil(n / 8) launches.  `out` (extension) may be `sample` itself."""
+        coefs = self.undo_coefs(int(timestep))
+        noises = [randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=sample.dtype) for _ in coefs]
+        return ops.repaint_undo(sample.contiguous(), noises, coefs, out=out)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        raise NotImplementedError('Use `DDPMScheduler.add_noise()` to train for sampling with RePaint.')
+
+
+@dataclass
 class ImagePipelineOutput:
     images: object
 
@@ -1013,6 +1157,91 @@ class PNDMPipeline(_PipelineBase):
             for t in self.progress_bar(ts):
                 model_output = fwd(image, t)
                 image = self.scheduler.step(model_output, t, image).prev_sample
+        finally:
+            fwd.close()
+        return _to_output(self, image, output_type, return_dict)
+
+
+def _pil_resample(name):
+    from PIL import Image
+    return getattr(getattr(Image, 'Resampling', Image), name)
+
+
+def _preprocess_image(image):
+    """pipeline_repaint.py:32-50: a tensor as it is; PIL images resized down to a multiple of 8 (Lanczos), scaled to [-1, 1], NCHW."""
+    from PIL import Image
+    if isinstance(image, torch.Tensor):
+        return image
+    if isinstance(image, Image.Image):
+        image = [image]
+    if isinstance(image[0], Image.Image):
+        w, h = image[0].size
+        w, h = (x - x % 8 for x in (w, h))
+        image = [np.array(i.resize((w, h), resample=_pil_resample('LANCZOS')))[None, :] for i in image]
+        image = np.concatenate(image, axis=0)
+        image = np.array(image).astype(np.float32) / 255.0
+        image = image.transpose(0, 3, 1, 2)
+        image = 2.0 * image - 1.0
+        image = torch.from_numpy(image)
+    elif isinstance(image[0], torch.Tensor):
+        image = torch.cat(image, dim=0)
+    return image
+
+
+def _preprocess_mask(mask):
+    """pipeline_repaint.py:53-70: a tensor as it is; PIL masks to grey, resized down to a multiple of 32 (nearest), made 0 / 1:
+    [N, H, W], which broadcasts against the image batch as [1, N, H, W]."""
+    from PIL import Image
+    if isinstance(mask, torch.Tensor):
+        return mask
+    if isinstance(mask, Image.Image):
+        mask = [mask]
+    if isinstance(mask[0], Image.Image):
+        w, h = mask[0].size
+        w, h = (x - x % 32 for x in (w, h))
+        mask = [np.array(m.convert('L').resize((w, h), resample=_pil_resample('NEAREST')))[None, :] for m in mask]
+        mask = np.concatenate(mask, axis=0)
+        mask = mask.astype(np.float32) / 255.0
+        mask[mask < 0.5] = 0
+        mask[mask >= 0.5] = 1
+        mask = torch.from_numpy(mask)
+    elif isinstance(mask[0], torch.Tensor):
+        mask = torch.cat(mask, dim=0)
+    return mask
+
+
+class RePaintPipeline(_PipelineBase):
+    """pipelines/repaint/pipeline_repaint.py:73-171: inpainting with an unconditional UNet.  Per entry of the scheduler's timestep
+    list either one UNet forward + one dp_repaint_step (the entry lies below the one before it) or one dp_repaint_undo (it lies
+    above: a jump back).  The loop runs over the scheduler's host list and reads nothing back; the state is updated in place."""
+
+    @torch.no_grad()
+    def __call__(self, image, mask_image, num_inference_steps=250, eta=0.0, jump_length=10, jump_n_sample=10, generator=None,
+                 output_type='pil', return_dict=True):
+        original_image = _preprocess_image(image).to(device=self.device, dtype=self.unet.dtype).contiguous()
+        mask_image = _preprocess_mask(mask_image).to(device=self.device, dtype=self.unet.dtype).contiguous()
+        batch_size = original_image.shape[0]
+        if isinstance(generator, list) and len(generator) != batch_size:
+            raise ValueError('You have passed a list of generators of length %d, but requested an effective batch size of %d. '
+                             'Make sure the batch size matches the length of the generators.' % (len(generator), batch_size))
+        shape = tuple(original_image.shape)
+        image = randn_tensor(shape, generator=generator, device=self.device, dtype=self.unet.dtype)
+        self.scheduler.set_timesteps(num_inference_steps, jump_length, jump_n_sample, self.device)
+        self.scheduler.eta = eta
+        ts = self.scheduler._ts                                               # the host's list: nothing is read back
+        n_calls = sum(1 for prev, t in zip([ts[0] + 1] + ts[:-1], ts) if t < prev)
+        t_last = ts[0] + 1
+        generator = generator[0] if isinstance(generator, list) else generator
+        fwd = _sampling_forward(self.unet, shape, n_calls)
+        try:
+            for t in self.progress_bar(ts):
+                if t < t_last:
+                    model_output = fwd(image, t)
+                    image = self.scheduler.step(model_output, t, image, original_image, mask_image, generator, out=image,
+                                                need_x0=False).prev_sample
+                else:
+                    image = self.scheduler.undo_step(image, t_last, generator, out=image)
+                t_last = t
         finally:
             fwd.close()
         return _to_output(self, image, output_type, return_dict)

@@ -2218,6 +2218,88 @@ def pndm_step(x, e, coef, mode, v_pred=False, acc=None, hist=(), out=None, hist_
     return out, hist_out
 
 
+REPAINT_MAX_BLOCKS = 4096            # DP_REPAINT_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
+REPAINT_UNDO_MAX = L.REPAINT_UNDO_MAX                       # DP_REPAINT_UNDO_MAX: re-noising steps chained in one launch
+REPAINT_COEF = ('sa', 'sb', 'sap', 's1', 'cd', 'sd')
+
+
+def repaint_mask_geometry(shape, mask_shape):
+    """(outer, stride, inner) of dp_repaint_step for a contiguous mask of `mask_shape` against data of `shape`: element i of the data
+    reads mask[(i // outer) * stride + i % inner].  The forms the kernel reads in place: the data's own shape (n, 0, n); the first
+    dimension kept or 1, then 1s, then the data's trailing dimensions -- [B,1,H,W], [1,1,H,W] (which [1,H,W] and [H,W] broadcast to),
+    [1,C,H,W].  None for any other broadcastable shape: the caller expands such a mask once.  A shape that does not broadcast to
+    `shape` is an AssertionError."""
+    shape, mask_shape = tuple(shape), tuple(mask_shape)
+    assert len(mask_shape) <= len(shape), 'repaint: the mask has more dimensions than the sample'
+    ms = (1,) * (len(shape) - len(mask_shape)) + mask_shape
+    assert all(m in (1, d) for m, d in zip(ms, shape)), 'repaint: mask %s does not broadcast to %s' % (mask_shape, shape)
+    n = math.prod(shape)
+    if ms == shape or n == 0:
+        return n, 0, n
+    j = len(shape)
+    while j > 1 and ms[j - 1] == shape[j - 1]:
+        j -= 1
+    if any(m != 1 for m in ms[1:j]):
+        return None
+    inner = math.prod(shape[j:])
+    if ms[0] == shape[0] and shape[0] > 1:
+        return n // shape[0], inner, inner
+    return n, 0, inner
+
+
+def repaint_step(x, e, noise, original, mask, coef, clip, add_noise, out=None, x0_out=None):
+    """One step of the RePaint scheduler (dp_repaint_step, csrc/repaint.hip).  `coef`: the host's fp32 scalars by name (REPAINT_COEF).
+    x0 = (x - sb e) / sa, clamped to [-1, 1] with `clip`; u = (sap x0 + cd e) + (sd noise with `add_noise`, else 0);
+    k = sap original + s1 noise; out = mask k + (1 - mask) u.  The mask is read in place when repaint_mask_geometry knows its shape
+    (any other broadcastable shape is the caller's to expand).  `out` may be `x`; no other buffer may be shared.  `x0_out`: a buffer
+    for x0, or True for a fresh one; None: x0 is not written.  Returns (out, x0_out)."""
+    n = x.numel()
+    for t in (x, e, noise, original, mask):
+        assert t.dtype == _f32 and t.is_contiguous() and t.device == x.device, 'repaint_step: contiguous fp32 tensors on one device'
+    assert e.numel() == n and noise.numel() == n and original.numel() == n
+    geo = repaint_mask_geometry(x.shape, mask.shape)
+    assert geo is not None, 'repaint_step: a mask of shape %s against %s is expanded by the caller' % (tuple(mask.shape), tuple(x.shape))
+    if out is None:
+        out = torch.empty_like(x)
+    if x0_out is True:
+        x0_out = torch.empty_like(x)
+    outs = [o for o in (out, x0_out) if o is not None]
+    for o in outs:
+        assert o.dtype == _f32 and o.is_contiguous() and o.numel() == n and o.device == x.device
+    ins = [t.data_ptr() for t in (e, noise, original, mask)]
+    assert out.data_ptr() not in ins and (x0_out is None or x0_out.data_ptr() not in ins + [x.data_ptr(), out.data_ptr()])
+    assert set(coef) == set(REPAINT_COEF), sorted(coef)
+    c = L.RepaintCoef(**{k: float(v) for k, v in coef.items()})
+    L.check(_lib().dp_repaint_step(_p(x), _p(e), _p(noise), _p(original), _p(mask), geo[0], geo[1], geo[2], 1 if clip else 0,
+                                   1 if add_noise else 0, C.byref(c), _p(out), _p(x0_out), n, _stream()), 'dp_repaint_step')
+    return out, x0_out
+
+
+def repaint_undo(x, noises, coefs, out=None):
+    """RePaint's undo_step (dp_repaint_undo): x = a_i x + b_i noises[i] for every (a_i, b_i) of `coefs` in turn, REPAINT_UNDO_MAX of
+    them per launch chained in registers (ceil(len / 8) launches; the launches after the first work on `out` in place).  `out` may
+    be `x`."""
+    n = x.numel()
+    noises, coefs = list(noises), [(float(a), float(b)) for a, b in coefs]
+    assert len(noises) == len(coefs) and len(noises) >= 1, 'repaint_undo: one (a, b) pair per noise tensor, at least one'
+    for t in [x] + noises:
+        assert t.dtype == _f32 and t.is_contiguous() and t.numel() == n and t.device == x.device, \
+            'repaint_undo: contiguous fp32 tensors on one device'
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == _f32 and out.is_contiguous() and out.numel() == n and out.device == x.device
+    assert out.data_ptr() not in [z.data_ptr() for z in noises]
+    src = x
+    for at in range(0, len(noises), REPAINT_UNDO_MAX):
+        zs, cs = noises[at:at + REPAINT_UNDO_MAX], coefs[at:at + REPAINT_UNDO_MAX]
+        c = L.RepaintUndoCoef()
+        for j, (z, (a, b)) in enumerate(zip(zs, cs)):
+            c.z[j], c.a[j], c.b[j] = z.data_ptr(), a, b
+        L.check(_lib().dp_repaint_undo(_p(src), C.byref(c), len(zs), _p(out), n, _stream()), 'dp_repaint_undo')
+        src = out
+    return out
+
+
 UNIPC_MAX_BLOCKS = 4096             # DP_UNIPC_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
 UNIPC_COEF = ('sigma_s', 'alpha_s', 'c_cx', 'c_c0', 'c_cB', 'c_rk1', 'c_rk2', 'c_rho1', 'c_rho2', 'c_rho_last',
               'p_cx', 'p_c0', 'p_cB', 'p_rk1', 'p_rk2', 'p_rho1', 'p_rho2')

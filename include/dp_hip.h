@@ -523,7 +523,7 @@ int dp_ddpm_step(const float* x, const float* eps, const float* vnoise, float sq
                  float c_xt, float sigma, int clip, float clip_range, float* out, long long n, void* stream);
 
 /* ---- The head / body / tail access rule of the elementwise step launchers below (dp_denoise_step, dp_cfg_denoise_step,
- * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
+ * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_repaint_step, dp_repaint_undo, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
  * When every pointer in use (a NULL or unread one does not count) shares one 4-byte-aligned phase modulo 16, a scalar head of
  * 0 .. 3 elements brings all of them to 16 bytes: the n4 = (n - head) / 4 groups after it take 16-byte accesses, the head and the
  * n - head - 4 n4 tail elements 4-byte ones.  Otherwise every access is 4 bytes (head = n).  Any n: long long indexing, one lane
@@ -665,6 +665,45 @@ typedef struct dp_pndm_coef {
 } dp_pndm_coef;
 int dp_pndm_step(const float* x, const float* e, float* acc, const float* h1, const float* h2, const float* h3, int mode, int v_pred,
                  const dp_pndm_coef* coef, float* x_next, float* hist_out, long long n, void* stream);
+
+/* The two kernels of the RePaint scheduler (csrc/repaint.hip; diffusers/schedulers/scheduling_repaint.py:250-293 step, :303-318
+ * undo_step) over n fp32 elements, one pass each, in the reference's operation order.
+ * dp_repaint_step: x the state, e the model output, z the noise of this step, o the original image, m the mask (1 = known):
+ *   x0  = (x - sb * e) / sa                       clamped to [-1, 1] when clip != 0; written to x0_out when that is not NULL
+ *   u   = (sap * x0 + cd * e) + (noise != 0 ? sd * z : 0)      (the reference adds a Python 0: -0 becomes +0)
+ *   k   = sap * o + s1 * z
+ *   out = m * k + (1 - m) * u
+ * Every operation rounded separately, a true division; the scalars are the host's 0-d fp32 arithmetic on the alphas_cumprod table
+ * (sa = alpha_prod_t ** 0.5, sb = beta_prod_t ** 0.5, sap = alpha_prod_t_prev ** 0.5, s1 = (1 - alpha_prod_t_prev) ** 0.5,
+ * cd = (1 - alpha_prod_t_prev - std_dev_t ** 2) ** 0.5, sd = std_dev_t = eta * variance ** 0.5).
+ * The mask is not materialised: element i reads m[(i / m_outer) * m_stride + (i % m_inner)], 1 <= m_inner <= m_outer,
+ * m_outer % m_inner == 0, m_stride >= 0 (and, with more than one image, m_stride == 0 or m_stride >= m_inner).  For data [B,C,H,W]:
+ * a mask of the data's shape (n, 0, n); [B,1,H,W] (CHW, HW, HW); [1,1,H,W] (n, 0, HW); [1,C,H,W] (n, 0, CHW).  m_inner >= n is the
+ * FULL form (16-byte loads of the mask, its pointer takes part in the head / body / tail rule above); any other is read with 4-byte
+ * loads, also where a 16-byte group of the data straddles a plane or an image.
+ * Aliases: `out` may be `x` itself.  Any other overlap between an output and another buffer (the mask's
+ * ((n - 1) / m_outer) * m_stride + m_inner elements included), a null pointer other than x0_out and a mask geometry outside the above
+ * are hipErrorInvalidValue: nothing is launched.  n <= 0 is a no-op.  At most DP_REPAINT_MAX_BLOCKS blocks.
+ * dp_repaint_undo: x = a[i] * x + b[i] * z[i] for i = 0 .. k - 1 (a[i] = (1 - beta) ** 0.5, b[i] = beta ** 0.5), chained in registers,
+ * each product and sum rounded separately: x is read once and written once.  1 <= k <= DP_REPAINT_UNDO_MAX; entries from k on are
+ * ignored.  `out` may be `x` itself; any other overlap of `out` with `x` or a z[i], a null pointer among those read and k outside
+ * the range are hipErrorInvalidValue. */
+#define DP_REPAINT_MAX_BLOCKS 4096
+#define DP_REPAINT_UNDO_MAX 8
+typedef struct dp_repaint_coef {
+    float sa, sb;                       /* the x0 prediction */
+    float sap, s1;                      /* alpha_prod_t_prev ** 0.5, (1 - alpha_prod_t_prev) ** 0.5 */
+    float cd, sd;                       /* the direction's factor, std_dev_t */
+} dp_repaint_coef;
+typedef struct dp_repaint_undo_coef {
+    const float* z[DP_REPAINT_UNDO_MAX];
+    float a[DP_REPAINT_UNDO_MAX];
+    float b[DP_REPAINT_UNDO_MAX];
+} dp_repaint_undo_coef;
+int dp_repaint_step(const float* x, const float* e, const float* z, const float* o, const float* m, long long m_outer,
+                    long long m_stride, long long m_inner, int clip, int noise, const dp_repaint_coef* coef, float* out,
+                    float* x0_out, long long n, void* stream);
+int dp_repaint_undo(const float* x, const dp_repaint_undo_coef* coef, int k, float* out, long long n, void* stream);
 
 /* x0 forming, dynamic thresholding and the DDPM / DDIM update for epsilon, sample and v-prediction models (csrc/threshold.hip;
  * diffusers/schedulers/scheduling_ddpm.py:278-310, :355-401, scheduling_ddim.py:205-237, :334-385) over B images of n fp32 elements.
