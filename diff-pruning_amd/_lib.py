@@ -117,6 +117,10 @@ class PndmCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'sc', 'd', 'den', 'c6', 'c3', 'c24')]
 
 
+class SigmaCoef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('s_noise', 'k', 'sig', 'c_out', 'c_den', 'dt', 'sigma_up')]
+
+
 class RepaintCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'sap', 's1', 'cd', 'sd')]
 
@@ -232,6 +236,9 @@ SIGNATURES = {
     'dp_pndm_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(PndmCoef), _vp, _vp, _ll, _vp],
     'dp_repaint_step': [_vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _i, _i, C.POINTER(RepaintCoef), _vp, _vp, _ll, _vp],
     'dp_repaint_undo': [_vp, C.POINTER(RepaintUndoCoef), _i, _vp, _ll, _vp],
+    'dp_sigma_step': [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(SigmaCoef), _vp, _vp, _ll, _vp],
+    'dp_sigma_scale': [_vp, _f, _vp, _ll, _vp],
+    'dp_sigma_add_noise': [_vp, _vp, _vp, _ll, _ll, _vp, _vp],
     'dp_x0_abs_quantile_workspace': [_ll, _ll],
     'dp_x0_abs_quantile': [_vp, _vp, _ll, _ll, _i, _f, _f, _ll, _ll, _f, _f, _i, _vp, _vp, _vp],
     'dp_x0_step': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(X0Coef), _vp, _vp, _ll, _ll, _vp],

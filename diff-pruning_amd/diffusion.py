@@ -11,6 +11,9 @@
   PNDMPipeline.__call__        pipelines/pndm/pipeline_pndm.py:47-99
   RePaintScheduler.step        scheduling_repaint.py:216-301 (HIP kernel dp_repaint_step), undo_step :303-318 (dp_repaint_undo)
   RePaintPipeline.__call__     pipelines/repaint/pipeline_repaint.py:82-171
+  EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, HeunDiscreteScheduler
+                               scheduling_euler_discrete.py, scheduling_euler_ancestral_discrete.py, scheduling_heun_discrete.py
+                               (HIP kernels dp_sigma_step, dp_sigma_scale, dp_sigma_add_noise; float64 timesteps, sample at scale sigma)
   randn_tensor                 utils/torch_utils.py:36-77   (CPU-generator semantics kept for seed parity)
 Host-side table arithmetic (1000-entry alpha-bar table) is fp32 torch on the CPU, exactly as in the reference.
 """
@@ -64,6 +67,13 @@ class _SchedulerBase:
 
     def scale_model_input(self, sample, *args, **kwargs):
         return sample
+
+    def host_timesteps(self):
+        """The current timestep table as a host list, in the form `step` takes them: the list a scheduler keeps beside its
+        `timesteps` tensor where it keeps one (ints for the multistep solvers and PNDM, floats -- mostly fractional -- for the
+        sigma-space schedulers), else one read-back of `timesteps` as ints.  What a sampling loop walks instead of the tensor."""
+        ts = getattr(self, '_ts', None)
+        return list(ts) if ts is not None else [int(t) for t in self.timesteps.tolist()]
 
     def _init_tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule, betas=None):
         self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule) if betas is None else betas
@@ -1012,6 +1022,361 @@ class RePaintScheduler(_SchedulerBase):
 
 
 @dataclass
+class EulerDiscreteSchedulerOutput:
+    prev_sample: torch.Tensor
+    pred_original_sample: torch.Tensor = None
+
+
+@dataclass
+class EulerAncestralDiscreteSchedulerOutput:
+    prev_sample: torch.Tensor
+    pred_original_sample: torch.Tensor = None
+
+
+class _SigmaSchedulerBase(_SchedulerBase):
+    """What the sigma-space (k-diffusion) schedulers share, and where a new one starts: the sample is carried at scale sigma
+    (`init_noise_sigma`, up to 157 for the CIFAR schedule), the model input is rescaled every step (`scale_model_input`, one launch of
+    dp_sigma_scale), the timesteps are float64 and mostly fractional, and `add_noise` is x0 + sigma * noise (dp_sigma_add_noise).
+    The timestep and sigma tables live as host lists (`_ts`, `_sig`) beside the `timesteps` / `sigmas` tensors: `step` and
+    `scale_model_input` look the index up on the host and read nothing back from the device.  The scalars of a step are 0-d fp32
+    torch arithmetic on the CPU in the reference's operation order, each `** 0.5`, log and exp correctly rounded (_rounded_once).
+    Outputs go into buffers of the scheduler's own, written in turn, so that a returned `prev_sample` stays valid while it is the
+    next step's input; the caller's `sample` and the model's output buffer are never written.
+    `sigma_space` is what a pipeline that neither scales its input nor starts from `init_noise_sigma` refuses by."""
+    sigma_space = True
+    order = 1
+    _WARNS_UNSCALED = True            # `step` before any `scale_model_input` warns once (the two Euler classes; Heun has no such warning)
+    _PRED = {'epsilon': ops.SIGMA_EPSILON, 'v_prediction': ops.SIGMA_V}
+    _sigma_to_t = DPMSolverMultistepScheduler._sigma_to_t
+    _convert_to_karras = DPMSolverMultistepScheduler._convert_to_karras
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+    def _init_sigma_tables(self):
+        cfg = self.config
+        if cfg.trained_betas is not None:
+            raise NotImplementedError('trained_betas is not on the hot path')
+        T = cfg.num_train_timesteps
+        self._init_tables(T, cfg.beta_start, cfg.beta_end, cfg.beta_schedule,
+                          _betas_for_alpha_bar(T) if cfg.beta_schedule == 'squaredcos_cap_v2' else None)
+        self.num_inference_steps = None
+        self.is_scale_input_called = False
+        self._warned = False
+        self._ring, self._turn = [None] * (self.order + 1), 0
+        self._x0 = self._scaled = self._deriv = None
+
+    def _train_sigmas(self):
+        """((1 - alphas_cumprod) / alphas_cumprod) ** 0.5 as an fp32 numpy array, ascending."""
+        return _rounded_once(torch.sqrt, (1 - self.alphas_cumprod) / self.alphas_cumprod).numpy()
+
+    def _log(self, a):
+        """np.log of an fp32 array or scalar, rounded once from fp64."""
+        return np.log(np.asarray(a, np.float64)).astype(np.float32)
+
+    def _karras(self, sigmas, log_sigmas, num_inference_steps):
+        sigmas = self._convert_to_karras(in_sigmas=sigmas, num_inference_steps=num_inference_steps)
+        return sigmas, np.array([self._sigma_to_t(sigma, log_sigmas) for sigma in sigmas])
+
+    def _set_tables(self, timesteps, sigmas, device=None):
+        """timesteps: float64, sigmas: fp32 with the trailing 0 (numpy); the host's copies and the index beside the tensors."""
+        assert timesteps.dtype == np.float64 and sigmas.dtype == np.float32
+        self._sig = torch.from_numpy(sigmas)                          # on the host: a step's scalars are 0-d views of it
+        self.sigmas = self._sig.to(device=device)
+        self.timesteps = torch.from_numpy(timesteps).to(device=device)
+        self._ts = [float(v) for v in timesteps]                      # what `step` and `scale_model_input` look timesteps up in
+        self._index = {}
+        for i, v in enumerate(self._ts):
+            self._index.setdefault(v, []).append(i)
+
+    def _matches(self, timestep):
+        """The table indices of a timestep: a Python number or a 0-d / 1-element tensor."""
+        if torch.is_tensor(timestep) and timestep.numel() != 1:
+            raise ValueError('timestep must be a number or a tensor with one element, got shape %s' % (tuple(timestep.shape),))
+        at = self._index.get(float(timestep))
+        if not at:
+            raise ValueError('timestep %r is not one of `scheduler.timesteps`' % (float(timestep),))
+        return at
+
+    def index_for_timestep(self, timestep):
+        at = self._matches(timestep)
+        if len(at) != 1:
+            raise ValueError('timestep %r is in `scheduler.timesteps` %d times' % (float(timestep), len(at)))
+        return at[0]
+
+    def _refuse_integers(self, timestep):
+        if isinstance(timestep, int) or (torch.is_tensor(timestep) and timestep.dtype in (torch.int32, torch.int64)):
+            raise ValueError('Passing integer indices (e.g. from `enumerate(timesteps)`) as timesteps to `EulerDiscreteScheduler.step()` '
+                             'is not supported. Make sure to pass one of the `scheduler.timesteps` as a timestep.')
+
+    def _prediction(self):
+        pt = self.config.prediction_type
+        if pt == 'sample':
+            raise NotImplementedError('prediction_type not implemented yet: sample')
+        if pt not in self._PRED:
+            raise ValueError('prediction_type given as %s must be one of `epsilon`, or `v_prediction`' % pt)
+        return self._PRED[pt]
+
+    def _begin_step(self, model_output, sample):
+        if model_output.shape[1] != sample.shape[1]:
+            raise NotImplementedError('learned-variance models are not part of this path')
+        if self._WARNS_UNSCALED and not self.is_scale_input_called and not self._warned:
+            import warnings
+            self._warned = True
+            warnings.warn('The `scale_model_input` function should be called before `step` to ensure correct denoising.')
+
+    @staticmethod
+    def _sqrt(v):
+        return _rounded_once(torch.sqrt, v)
+
+    def _v_coefs(self, c, sigma):
+        if self.config.prediction_type == 'v_prediction':
+            c['c_out'], c['c_den'] = -sigma / self._sqrt(sigma ** 2 + 1), sigma ** 2 + 1
+        return c
+
+    @staticmethod
+    def _fits(buf, like):
+        return buf is not None and buf.shape == like.shape and buf.device == like.device and buf.dtype == like.dtype
+
+    def _own(self, name, like):
+        buf = getattr(self, name)
+        if not self._fits(buf, like):
+            buf = torch.empty_like(like, memory_format=torch.contiguous_format)
+            setattr(self, name, buf)
+        return buf
+
+    def _next_buffer(self, like, *keep):
+        """The ring buffer that takes this step's prev_sample: never one that `keep` (the sample, Heun's saved sample) lives in."""
+        held = {t.data_ptr() for t in keep if t is not None}
+        for _ in range(len(self._ring)):
+            self._turn = (self._turn + 1) % len(self._ring)
+            buf = self._ring[self._turn]
+            if not self._fits(buf, like):
+                buf = self._ring[self._turn] = torch.empty_like(like, memory_format=torch.contiguous_format)
+            if buf.data_ptr() not in held:
+                return buf
+        raise RuntimeError('no free output buffer: not a state that `step` reaches')
+
+    def _draw(self, model_output, generator, needed):
+        """The reference's randn_tensor(model_output.shape, dtype, device, generator), so that a generator's stream advances as the
+        reference's does; a draw that no kernel reads is made where the generator lives and not uploaded."""
+        e = model_output
+        if not needed and generator is not None and e.device.type != 'cpu':
+            g = generator[0] if isinstance(generator, list) else generator
+            if g.device.type == 'cpu':
+                randn_tensor(e.shape, generator=generator, device='cpu', dtype=e.dtype)
+                return None
+        z = randn_tensor(e.shape, generator=generator, device=e.device, dtype=e.dtype)
+        return z.contiguous() if needed else None
+
+    def scale_model_input(self, sample, timestep):
+        """sample / ((sigma**2 + 1) ** 0.5) into a buffer of this scheduler's own: one launch."""
+        sigma = self._sig[self.index_for_timestep(timestep)]
+        out = ops.sigma_scale(sample.contiguous(), float(self._sqrt(sigma ** 2 + 1)), out=self._own('_scaled', sample))
+        self.is_scale_input_called = True
+        return out
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """original_samples + noise * sigma, one sigma per image looked up on the host."""
+        if original_samples.device.type != 'cuda':
+            raise RuntimeError('add_noise runs on the HIP kernels: tensors must live on a cuda device')
+        sig = self.noise_sigmas(timesteps)
+        if len(sig) != original_samples.shape[0]:
+            raise ValueError('add_noise: %d timesteps for %d images' % (len(sig), original_samples.shape[0]))
+        return ops.sigma_add_noise(original_samples.contiguous(), noise.contiguous(), sig.to(original_samples.device))
+
+    def noise_sigmas(self, timesteps):
+        """The sigma of every timestep of `timesteps` (a tensor or a list), looked up on the host: an fp32 host tensor."""
+        ts = timesteps.reshape(-1).tolist() if torch.is_tensor(timesteps) else list(timesteps)
+        return self._sig[[self.index_for_timestep(t) for t in ts]].contiguous()
+
+
+class _EulerTables(_SigmaSchedulerBase):
+    """The tables the two Euler classes share: the constructor's (all training timesteps, `init_noise_sigma` from them and not
+    updated afterwards) and `set_timesteps` (the ancestral class has neither `interpolation_type` nor `use_karras_sigmas`)."""
+
+    def _init_euler(self):
+        self._init_sigma_tables()
+        T = self.config.num_train_timesteps
+        sigmas = np.concatenate([self._train_sigmas()[::-1], [0.0]]).astype(np.float32)
+        self._set_tables(np.linspace(0, T - 1, T, dtype=float)[::-1].copy(), sigmas)
+        self.init_noise_sigma = self.sigmas.max()
+        self.use_karras_sigmas = getattr(self.config, 'use_karras_sigmas', False)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """scheduling_euler_discrete.py:182-218 with the reference's numpy expressions."""
+        cfg = self.config
+        interpolation = getattr(cfg, 'interpolation_type', 'linear')
+        if interpolation not in ('linear', 'log_linear'):
+            raise ValueError("%s is not implemented. Please specify interpolation_type to either 'linear' or 'log_linear'" % interpolation)
+        self.num_inference_steps = num_inference_steps
+        timesteps = np.linspace(0, cfg.num_train_timesteps - 1, num_inference_steps, dtype=float)[::-1].copy()
+        sigmas = self._train_sigmas()
+        log_sigmas = self._log(sigmas)
+        if interpolation == 'linear':
+            sigmas = np.interp(timesteps, np.arange(0, len(sigmas)), sigmas)
+        else:                                                         # n + 1 sigmas for n timesteps, as the reference has it
+            ramp = torch.linspace(float(self._log(sigmas[-1])), float(self._log(sigmas[0])), num_inference_steps + 1)
+            sigmas = _rounded_once(torch.exp, ramp).numpy()
+        if self.use_karras_sigmas:
+            sigmas, timesteps = self._karras(sigmas, log_sigmas, num_inference_steps)
+        self._set_tables(timesteps, np.concatenate([sigmas, [0.0]]).astype(np.float32), device)
+
+
+class EulerDiscreteScheduler(_EulerTables):
+    """scheduling_euler_discrete.py:79-383, Algorithm 2 of Karras et al. (2022) with its churn, for epsilon, `v_prediction` and `sample`
+    models, `interpolation_type` linear / log_linear (whose table has n + 2 entries for n timesteps, as the reference's has) and
+    `use_karras_sigmas`.  One launch of dp_sigma_step per `step`.  `init_noise_sigma` is the training table's maximum and is not
+    updated by `set_timesteps`.  The noise is drawn on every step, as the reference draws it; without churn it is not used.
+    With churn and `v_prediction` the conversion uses sigma, not sigma_hat, as the reference does.
+    Not carried (NotImplementedError): `trained_betas`, models that predict a variance."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'prediction_type',
+                    'interpolation_type', 'use_karras_sigmas')
+    _PRED = dict(_SigmaSchedulerBase._PRED, sample=ops.SIGMA_SAMPLE, original_sample=ops.SIGMA_SAMPLE)
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', trained_betas=None,
+                 prediction_type='epsilon', interpolation_type='linear', use_karras_sigmas=False):
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type,
+                                      interpolation_type=interpolation_type, use_karras_sigmas=use_karras_sigmas)
+        self._init_euler()
+
+    def step_coefs(self, index, gamma=0.0, s_noise=1.0):
+        """The fp32 scalars of :317-347 as ops.sigma_step names them, for table index `index`."""
+        sigma = self._sig[index]
+        sigma_hat = sigma * (gamma + 1)
+        c = dict(sig=sigma_hat, dt=self._sig[index + 1] - sigma_hat)
+        if gamma > 0:
+            c['k'], c['s_noise'] = self._sqrt(sigma_hat ** 2 - sigma ** 2), torch.tensor(s_noise, dtype=torch.float32)
+        return {k: float(v) for k, v in self._v_coefs(c, sigma).items()}
+
+    def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float('inf'), s_noise=1.0, generator=None,
+             return_dict=True):
+        self._refuse_integers(timestep)
+        pt = self.config.prediction_type
+        if pt not in self._PRED:
+            raise ValueError('prediction_type given as %s must be one of `epsilon`, or `v_prediction`' % pt)
+        self._begin_step(model_output, sample)
+        i = self.index_for_timestep(timestep)
+        sigma = self._sig[i]
+        gamma = min(s_churn / (len(self._sig) - 1), 2 ** 0.5 - 1) if s_tmin <= sigma <= s_tmax else 0.0
+        noise = self._draw(model_output, generator, gamma > 0)
+        prev, x0 = ops.sigma_step(sample.contiguous(), model_output.contiguous(), self.step_coefs(i, gamma, s_noise), ops.SIGMA_EULER,
+                                  self._PRED[pt], noise=noise, out=self._next_buffer(sample, sample), aux_out=self._own('_x0', sample))
+        if not return_dict:
+            return (prev,)
+        return EulerDiscreteSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+
+class EulerAncestralDiscreteScheduler(_EulerTables):
+    """scheduling_euler_ancestral_discrete.py:79-309: ancestral sampling with Euler steps for epsilon and `v_prediction` models; the
+    noise is drawn after the update, as the reference draws it.  One launch of dp_sigma_step per `step`.
+    Not carried: `trained_betas`, models that predict a variance (NotImplementedError); `sample` models (the reference's
+    NotImplementedError from `step`)."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'prediction_type')
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', trained_betas=None,
+                 prediction_type='epsilon'):
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type)
+        self._init_euler()
+
+    def step_coefs(self, index):
+        """The fp32 scalars of :243-266 as ops.sigma_step names them, and `sigma_down`, which only the host reads."""
+        sigma_from, sigma_to = self._sig[index], self._sig[index + 1]
+        sigma_up = self._sqrt(sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2)
+        sigma_down = self._sqrt(sigma_to ** 2 - sigma_up ** 2)
+        c = dict(sig=sigma_from, dt=sigma_down - sigma_from, sigma_up=sigma_up, sigma_down=sigma_down)
+        return {k: float(v) for k, v in self._v_coefs(c, sigma_from).items()}
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True):
+        self._refuse_integers(timestep)
+        pred = self._prediction()
+        self._begin_step(model_output, sample)
+        c = self.step_coefs(self.index_for_timestep(timestep))
+        del c['sigma_down']
+        noise = self._draw(model_output, generator, True)
+        prev, x0 = ops.sigma_step(sample.contiguous(), model_output.contiguous(), c, ops.SIGMA_ANCESTRAL, pred, noise=noise,
+                                  out=self._next_buffer(sample, sample), aux_out=self._own('_x0', sample))
+        if not return_dict:
+            return (prev,)
+        return EulerAncestralDiscreteSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+
+class HeunDiscreteScheduler(_SigmaSchedulerBase):
+    """scheduling_heun_discrete.py:53-351, Algorithm 1 of Karras et al. (2022) without churn, for epsilon and `v_prediction` models:
+    two model calls per step but the last, so both tables are doubled (2n - 1 timesteps, 2n sigmas).  `state_in_first_order`,
+    `prev_derivative`, `dt` and `sample` are kept as the reference keeps them; the sample of the first call is held by reference, not
+    copied.  One launch of dp_sigma_step per `step`.  `init_noise_sigma` follows `set_timesteps`.
+    Not carried: `trained_betas`, models that predict a variance (NotImplementedError); `sample` models (the reference's
+    NotImplementedError from `step`)."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'prediction_type',
+                    'use_karras_sigmas')
+    order = 2
+    _WARNS_UNSCALED = False
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule='linear', trained_betas=None,
+                 prediction_type='epsilon', use_karras_sigmas=False):
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type,
+                                      use_karras_sigmas=use_karras_sigmas)
+        self._init_sigma_tables()
+        self.use_karras_sigmas = use_karras_sigmas    # (the reference's constructor reads it from the config before it is set)
+        self.set_timesteps(num_train_timesteps)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """:150-197 with the reference's numpy expressions; the running values reset."""
+        self.num_inference_steps = num_inference_steps
+        timesteps = np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps, dtype=float)[::-1].copy()
+        sigmas = self._train_sigmas()
+        log_sigmas = self._log(sigmas)
+        sigmas = np.interp(timesteps, np.arange(0, len(sigmas)), sigmas)
+        if self.use_karras_sigmas:
+            sigmas, timesteps = self._karras(sigmas, log_sigmas, num_inference_steps)
+        sigmas = np.concatenate([sigmas, [0.0]]).astype(np.float32)
+        sigmas = np.concatenate([sigmas[:1], sigmas[1:-1].repeat(2), sigmas[-1:]])
+        timesteps = np.concatenate([timesteps[:1], timesteps[1:].repeat(2)])
+        self._set_tables(timesteps, sigmas, device)
+        self.init_noise_sigma = self.sigmas.max()
+        self.prev_derivative = self.dt = self.sample = None
+
+    @property
+    def state_in_first_order(self):
+        return self.dt is None
+
+    def index_for_timestep(self, timestep):
+        """The last match in first-order state, the first otherwise (:119-129)."""
+        return self._matches(timestep)[-1 if self.state_in_first_order else 0]
+
+    def step_coefs(self, index):
+        """The fp32 scalars of :263-309 as ops.sigma_step names them, for the state the scheduler is in."""
+        if self.state_in_first_order:
+            sigma, sigma_next = self._sig[index], self._sig[index + 1]
+        else:
+            sigma, sigma_next = self._sig[index - 1], self._sig[index]
+        sigma_hat = sigma * (0 + 1)
+        sigma_input = sigma_hat if self.state_in_first_order else sigma_next
+        c = dict(sig=sigma_input, dt=sigma_next - sigma_hat if self.state_in_first_order else self.dt)
+        return {k: float(v) for k, v in self._v_coefs(c, sigma_input).items()}
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        pred = self._prediction()
+        self._begin_step(model_output, sample)
+        c = self.step_coefs(self.index_for_timestep(timestep))
+        x, e = sample.contiguous(), model_output.contiguous()
+        if self.state_in_first_order:
+            prev, d = ops.sigma_step(x, e, c, ops.SIGMA_HEUN1, pred, out=self._next_buffer(sample, sample), aux_out=self._own('_deriv', sample))
+            self.prev_derivative, self.dt, self.sample = d, torch.tensor(c['dt'], dtype=torch.float32), sample
+        else:
+            prev, _ = ops.sigma_step(x, e, c, ops.SIGMA_HEUN2, pred, d1=self.prev_derivative, saved=self.sample.contiguous(),
+                                     out=self._next_buffer(sample, sample, self.sample))
+            self.prev_derivative = self.dt = self.sample = None
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
+@dataclass
 class ImagePipelineOutput:
     images: object
 
@@ -1093,6 +1458,11 @@ class DDPMPipeline(_PipelineBase):
 
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, num_inference_steps=1000, output_type='pil', return_dict=True):
+        if getattr(self.scheduler, 'sigma_space', False):
+            # the reference would sample without scale_model_input and without init_noise_sigma here, and only warn
+            raise ValueError('%s carries the sample at scale sigma: DDPMPipeline neither scales the model input nor starts from '
+                             'init_noise_sigma.  Use LDMPipeline, or the explicit loop over unet.sampling_forward: '
+                             'scale_model_input, the model, step (README.md)' % type(self.scheduler).__name__)
         shape = _image_shape(self.unet, batch_size)
         image = randn_tensor(shape, generator=generator, device=self.device)
         self.scheduler.set_timesteps(num_inference_steps)
@@ -1273,7 +1643,7 @@ class LDMPipeline(_PipelineBase):
             latents = latents * self.scheduler.init_noise_sigma
         self.scheduler.set_timesteps(num_inference_steps)
         extra = {'eta': eta} if 'eta' in inspect.signature(self.scheduler.step).parameters else {}
-        ts = [int(t) for t in self.scheduler.timesteps.tolist()]
+        ts = self.scheduler.host_timesteps()                          # ints as before; the sigma-space schedulers' floats as they are
         fwd = _sampling_forward(self.unet, shape, len(ts))
         try:
             for t in self.progress_bar(ts):

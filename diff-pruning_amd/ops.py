@@ -2300,6 +2300,78 @@ def repaint_undo(x, noises, coefs, out=None):
     return out
 
 
+SIGMA_MAX_BLOCKS = 4096              # DP_SIGMA_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
+SIGMA_COEF = ('s_noise', 'k', 'sig', 'c_out', 'c_den', 'dt', 'sigma_up')
+SIGMA_EULER, SIGMA_ANCESTRAL, SIGMA_HEUN1, SIGMA_HEUN2 = range(4)            # DP_SIGMA_* (include/dp_hip.h): the values of `mode`
+SIGMA_EPSILON, SIGMA_V, SIGMA_SAMPLE = range(3)                              # ... and of `pred`
+# the (mode, pred) pairs the library instantiates: `sample` models on the Euler step only, as in the reference
+SIGMA_INSTANCES = tuple((m, p) for m in range(4) for p in range(3) if p != SIGMA_SAMPLE or m == SIGMA_EULER)
+
+
+def sigma_step(x, e, coef, mode, pred=SIGMA_EPSILON, noise=None, d1=None, saved=None, out=None, aux_out=None):
+    """One call of a sigma-space scheduler's `step` (dp_sigma_step, csrc/sigma.hip) over flat fp32 data.  `coef`: the host's fp32
+    scalars by name (SIGMA_COEF; one the instantiation does not read may be left out).  x0 = xh - sig e (SIGMA_EPSILON) |
+    e c_out + xh / c_den (SIGMA_V) | e (SIGMA_SAMPLE, EULER only); d = (xh - x0) / sig.
+    EULER: xh = x + (noise s_noise) k with `noise`, else x; out = xh + d dt; aux = x0.   ANCESTRAL (needs `noise`):
+    out = (x + d dt) + noise sigma_up; aux = x0.   HEUN1: out = x + d dt; aux = d.   HEUN2 (needs `d1`, `saved`):
+    out = saved + ((d1 + d) / 2) dt; no aux.  `out` may be `x`, in HEUN2 `saved`; no other buffer may be shared.
+    Returns (out, aux), aux None in HEUN2."""
+    n = x.numel()
+    assert (mode, pred) in SIGMA_INSTANCES, (mode, pred)
+    assert x.dtype == _f32 and e.dtype == _f32 and x.is_contiguous() and e.is_contiguous() and e.numel() == n
+    if mode not in (SIGMA_EULER, SIGMA_ANCESTRAL):
+        noise = None
+    if mode != SIGMA_HEUN2:
+        d1 = saved = None
+    assert mode != SIGMA_ANCESTRAL or noise is not None, 'sigma_step: the ancestral step without noise'
+    assert mode != SIGMA_HEUN2 or (d1 is not None and saved is not None), 'sigma_step: the second Heun stage without d1 / saved'
+    ins = [t for t in (e, noise, d1) if t is not None]
+    for t in ins + [t for t in (saved,) if t is not None]:
+        assert t.dtype == _f32 and t.is_contiguous() and t.numel() == n and t.device == x.device, \
+            'sigma_step: contiguous fp32 tensors of one size on one device'
+    if out is None:
+        out = torch.empty_like(x)
+    if mode == SIGMA_HEUN2:
+        aux_out = None
+    elif aux_out is None:
+        aux_out = torch.empty_like(x)
+    for o in (out, aux_out):
+        assert o is None or (o.dtype == _f32 and o.is_contiguous() and o.numel() == n and o.device == x.device)
+    assert out.data_ptr() not in [t.data_ptr() for t in ins]
+    assert aux_out is None or aux_out.data_ptr() not in [t.data_ptr() for t in ins + [x, out]]
+    unknown = set(coef) - set(SIGMA_COEF)
+    assert not unknown, unknown
+    c = L.SigmaCoef(**{k: float(v) for k, v in coef.items()})
+    L.check(_lib().dp_sigma_step(_p(x), _p(e), _p(noise), _p(d1), _p(saved), int(mode), int(pred), C.byref(c), _p(out), _p(aux_out),
+                                 n, _stream()), 'dp_sigma_step')
+    return out, aux_out
+
+
+def sigma_scale(x, c, out=None):
+    """scale_model_input of the sigma-space schedulers (dp_sigma_scale): out = x / c, a true division.  `out` may be `x`."""
+    assert x.dtype == _f32 and x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == _f32 and out.is_contiguous() and out.numel() == x.numel() and out.device == x.device
+    L.check(_lib().dp_sigma_scale(_p(x), float(c), _p(out), x.numel(), _stream()), 'dp_sigma_scale')
+    return out
+
+
+def sigma_add_noise(x0, noise, sigma, out=None):
+    """add_noise of the sigma-space schedulers (dp_sigma_add_noise): out[b] = x0[b] + noise[b] * sigma[b], `sigma` one fp32 value per
+    image on the data's device.  `out` shares no buffer."""
+    B = x0.shape[0]
+    for t in (x0, noise, sigma):
+        assert t.dtype == _f32 and t.is_contiguous() and t.device == x0.device, 'sigma_add_noise: contiguous fp32 tensors on one device'
+    assert noise.numel() == x0.numel() and sigma.numel() == B and B > 0 and x0.numel() > 0
+    if out is None:
+        out = torch.empty_like(x0)
+    assert out.dtype == _f32 and out.is_contiguous() and out.numel() == x0.numel() and out.device == x0.device
+    assert out.data_ptr() not in (x0.data_ptr(), noise.data_ptr(), sigma.data_ptr())
+    L.check(_lib().dp_sigma_add_noise(_p(x0), _p(noise), _p(sigma), B, x0.numel() // B, _p(out), _stream()), 'dp_sigma_add_noise')
+    return out
+
+
 UNIPC_MAX_BLOCKS = 4096             # DP_UNIPC_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
 UNIPC_COEF = ('sigma_s', 'alpha_s', 'c_cx', 'c_c0', 'c_cB', 'c_rk1', 'c_rk2', 'c_rho1', 'c_rho2', 'c_rho_last',
               'p_cx', 'p_c0', 'p_cB', 'p_rk1', 'p_rk2', 'p_rho1', 'p_rho2')

@@ -8,6 +8,8 @@ key names, with every weight held by a real `nn.Conv2d` / `nn.Linear` / `nn.Grou
 Those layer objects are *parameter holders only*: their own `forward` is never called; all arithmetic
 runs in the HIP kernels through `UNetEngine`.  There is no PyTorch fallback.
 """
+import numbers
+
 import torch
 import torch.nn as nn
 
@@ -223,6 +225,9 @@ class UNet2DModel(DiffusersModel):
     def sampling_forward(self, shape, n_calls, replay=None):
         """The no-grad forward of a sampling loop (pipeline_ddim.py:101-116, pipeline_ddpm.py:87-96) as a callable
         `f(sample, t: int) -> eps` plus `f.close()`.  The weights are frozen for the lifetime of `f` (`pin_weights`).
+        `t` may also be a Python float or a floating tensor with one element -- a fractional timestep of the sigma-space
+        schedulers (979.61): the model is then conditioned on float32(t) for every image, as the reference's
+        `timesteps[:, None].float()` conditions it; an int or a long tensor keeps its launches and its bits.
         With `replay` (default: automatic -- a cuda model in eval mode without foreign forward hooks, called at least
         REPLAY_MIN_CALLS times; DP_SAMPLE_REPLAY=0 never, =1 from the first call) the forward is captured ONCE at `shape` and every
         call re-issues its ~180 launches from the library's C loop (ops.CapturedCall, csrc/replay.hip): same kernels, same
@@ -408,6 +413,8 @@ class _EagerForward:
         self._pin.__enter__()
 
     def __call__(self, sample, t):
+        if _is_fractional(t):                              # float32(t) for every image: the reference's timesteps[:, None].float()
+            t = _fractional_timesteps(t, sample.shape[0], sample.device)
         return self.model(sample, t).sample
 
     def close(self):
@@ -416,12 +423,33 @@ class _EagerForward:
             self._pin = None
 
 
+def _is_fractional(t):
+    """A timestep of the sigma-space schedulers: a real number that is no integer type (a Python float, numpy's float32 / float64
+    scalars) or a floating tensor with one element.  An int, a numpy integer or a long tensor is an index into the training table
+    and keeps its own path."""
+    if torch.is_tensor(t):
+        return t.is_floating_point() and t.numel() == 1
+    return isinstance(t, numbers.Real) and not isinstance(t, numbers.Integral)
+
+
+def _fractional_timesteps(t, batch, device, out=None):
+    """[batch] fp32 on `device`, every entry float32(t); into `out` when given.  Nothing is read back."""
+    if out is None:
+        out = torch.empty(batch, dtype=torch.float32, device=device)
+    if torch.is_tensor(t):
+        out.copy_(t.detach().reshape(1).expand(batch))     # casts to fp32 on the way (float64 -> float32, rounded once)
+    else:
+        out.fill_(float(t))
+    return out
+
+
 class _CapturedForward:
     """One captured no-grad forward at a fixed [B, C, H, W], replayed natively (UNet2DModel.sampling_forward)."""
 
     def __init__(self, model, shape):
         from . import ops
         self.model = model
+        self.call_f = self.tf = None                       # the capture for fractional timesteps and its float buffer
         self._pin = model.pin_weights()
         self._pin.__enter__()
         try:
@@ -443,17 +471,35 @@ class _CapturedForward:
             # the capture holds the ADDRESSES of the pinned packed operands: after close() they may have been freed or recycled
             raise RuntimeError('sampling_forward: called after close() (the captured forward\'s packed operands are no longer pinned)')
         self.x.copy_(sample)
+        if _is_fractional(t):
+            return self._fractional_call(t).launch()
         if torch.is_tensor(t) and t.dim() > 0 and t.numel() > 1:
             self.t.copy_(t)
         else:
             self.t.fill_(int(t))
         return self.call.launch()          # a tensor of the capture's pool: valid until the next call
 
+    def _fractional_call(self, t):
+        """The capture that reads its timesteps from a float buffer, made on the first fractional timestep (the integer capture
+        embeds `long -> float32`, one launch more, and stays as it is)."""
+        if self.call_f is None:
+            from . import ops
+            eng = self._pin.eng
+            self.tf = _fractional_timesteps(t, self.x.shape[0], self.x.device)
+            with torch.no_grad():
+                eng.forward(self.x, self.tf, save=False)             # eager once, as for the integer capture
+                # no prepare_packs() here: the constructor packed every operand for the integer capture, the weights are pinned
+                # since then, and the two forwards differ only in the timestep buffer's dtype, which asks for no operand
+                self.call_f = ops.CapturedCall(lambda: eng.forward(self.x, self.tf, save=False))
+        else:
+            _fractional_timesteps(t, self.x.shape[0], self.x.device, out=self.tf)
+        return self.call_f
+
     def close(self):
         if self._pin is not None:
             if getattr(self, 'call', None) is not None:
                 torch.cuda.synchronize(self.model.device)    # no replayed launch may still read the operands about to be unpinned
-                self.call = None                             # ... or the capture's pool, which goes with the graph
+                self.call = self.call_f = None               # ... or the capture's pool, which goes with the graph
             self._pin.__exit__(None, None, None)
             self._pin = None
 

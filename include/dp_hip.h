@@ -523,7 +523,7 @@ int dp_ddpm_step(const float* x, const float* eps, const float* vnoise, float sq
                  float c_xt, float sigma, int clip, float clip_range, float* out, long long n, void* stream);
 
 /* ---- The head / body / tail access rule of the elementwise step launchers below (dp_denoise_step, dp_cfg_denoise_step,
- * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_repaint_step, dp_repaint_undo, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
+ * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_repaint_step, dp_repaint_undo, dp_sigma_step and its two companions, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
  * When every pointer in use (a NULL or unread one does not count) shares one 4-byte-aligned phase modulo 16, a scalar head of
  * 0 .. 3 elements brings all of them to 16 bytes: the n4 = (n - head) / 4 groups after it take 16-byte accesses, the head and the
  * n - head - 4 n4 tail elements 4-byte ones.  Otherwise every access is 4 bytes (head = n).  Any n: long long indexing, one lane
@@ -704,6 +704,46 @@ int dp_repaint_step(const float* x, const float* e, const float* z, const float*
                     long long m_stride, long long m_inner, int clip, int noise, const dp_repaint_coef* coef, float* out,
                     float* x0_out, long long n, void* stream);
 int dp_repaint_undo(const float* x, const dp_repaint_undo_coef* coef, int k, float* out, long long n, void* stream);
+
+/* The three kernels of the sigma-space (k-diffusion) schedulers (csrc/sigma.hip; diffusers/schedulers/scheduling_euler_discrete.py
+ * :305-349, scheduling_euler_ancestral_discrete.py:233-273, scheduling_heun_discrete.py:261-318) over n fp32 elements, one pass each,
+ * in the reference's operation order.  The state is carried at scale sigma (up to 157 for the CIFAR schedule).
+ * dp_sigma_step: x the sample, e the model output, z the noise, d1 the derivative DP_SIGMA_HEUN1 wrote, xs the sample it was handed.
+ *   x0 from xh:  DP_SIGMA_EPSILON  xh - sig * e;   DP_SIGMA_V  e * c_out + xh / c_den;   DP_SIGMA_SAMPLE (EULER only)  e
+ *   DP_SIGMA_EULER      xh = z ? x + (z * s_noise) * k : x;  d = (xh - x0) / sig;  x_next = xh + d * dt;             aux_out = x0
+ *   DP_SIGMA_ANCESTRAL  xh = x;  d = (x - x0) / sig;  x_next = (x + d * dt) + z * sigma_up;                           aux_out = x0
+ *   DP_SIGMA_HEUN1      xh = x;  d = (x - x0) / sig;  x_next = x + d * dt;                                            aux_out = d
+ *   DP_SIGMA_HEUN2      xh = x;  d2 = (x - x0) / sig;  d = (d1 + d2) / 2;  x_next = xs + d * dt                       (no aux_out)
+ * Every operation rounded separately, true divisions; the scalars are the host's 0-d fp32 arithmetic on the sigma table: sig =
+ * sigma_hat (EULER, HEUN1), sigma (ANCESTRAL), sigma_next (HEUN2); k = (sigma_hat^2 - sigma^2) ** 0.5; c_out = -s / (s^2 + 1) ** 0.5
+ * and c_den = s^2 + 1 for s = sig (EULER: s = sigma, also with churn, as the reference has it); dt; sigma_up.  z == NULL in EULER: no
+ * churn.  A pointer the mode neither reads nor writes is ignored and may be NULL.
+ * Aliases: `x_next` may be `x` itself, and in HEUN2 `xs` itself: each lane reads every input of its elements before it writes any
+ * of them, and no other lane touches them.  Any other overlap between an output and another buffer is hipErrorInvalidValue, as are
+ * a null pointer that the mode reads or writes, a mode outside 0 .. 3, a type outside 0 .. 2 and DP_SIGMA_SAMPLE outside EULER:
+ * nothing is launched.  n <= 0 is a no-op.
+ * dp_sigma_scale: out = x / c (scale_model_input; c = (sigma^2 + 1) ** 0.5 from the host).  `out` may be `x` itself.
+ * dp_sigma_add_noise: out[b][i] = x0[b][i] + z[b][i] * sigma[b] for B images of `per` elements, sigma a device vector of B fp32
+ * values; `out` overlaps nothing.
+ * Accesses: the head / body / tail rule above, at most DP_SIGMA_MAX_BLOCKS blocks. */
+#define DP_SIGMA_MAX_BLOCKS 4096
+#define DP_SIGMA_EULER 0
+#define DP_SIGMA_ANCESTRAL 1
+#define DP_SIGMA_HEUN1 2
+#define DP_SIGMA_HEUN2 3
+#define DP_SIGMA_EPSILON 0
+#define DP_SIGMA_V 1
+#define DP_SIGMA_SAMPLE 2
+typedef struct dp_sigma_coef {
+    float s_noise, k;                   /* the churn (EULER with z) */
+    float sig;                          /* the sigma of the conversion and of the derivative */
+    float c_out, c_den;                 /* the v-conversion (DP_SIGMA_V only) */
+    float dt, sigma_up;                 /* the update; sigma_up: ANCESTRAL only */
+} dp_sigma_coef;
+int dp_sigma_step(const float* x, const float* e, const float* z, const float* d1, const float* xs, int mode, int pred,
+                  const dp_sigma_coef* coef, float* x_next, float* aux_out, long long n, void* stream);
+int dp_sigma_scale(const float* x, float c, float* out, long long n, void* stream);
+int dp_sigma_add_noise(const float* x0, const float* z, const float* sigma, long long B, long long per, float* out, void* stream);
 
 /* x0 forming, dynamic thresholding and the DDPM / DDIM update for epsilon, sample and v-prediction models (csrc/threshold.hip;
  * diffusers/schedulers/scheduling_ddpm.py:278-310, :355-401, scheduling_ddim.py:205-237, :334-385) over B images of n fp32 elements.
