@@ -121,6 +121,14 @@ class SigmaCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('s_noise', 'k', 'sig', 'c_out', 'c_den', 'dt', 'sigma_up')]
 
 
+class Kdpm2Coef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sig', 'c_out', 'c_den', 'dt', 'sigma_up')]
+
+
+class LmsCoef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sig', 'c_out', 'c_den', 'c0', 'c1', 'c2', 'c3')]
+
+
 class RepaintCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'sap', 's1', 'cd', 'sd')]
 
@@ -239,6 +247,8 @@ SIGNATURES = {
     'dp_sigma_step': [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(SigmaCoef), _vp, _vp, _ll, _vp],
     'dp_sigma_scale': [_vp, _f, _vp, _ll, _vp],
     'dp_sigma_add_noise': [_vp, _vp, _vp, _ll, _ll, _vp, _vp],
+    'dp_kdpm2_step': [_vp, _vp, _vp, _vp, _i, C.POINTER(Kdpm2Coef), _vp, _ll, _vp],
+    'dp_lms_step': [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LmsCoef), _vp, _vp, _vp, _ll, _vp],
     'dp_x0_abs_quantile_workspace': [_ll, _ll],
     'dp_x0_abs_quantile': [_vp, _vp, _ll, _ll, _i, _f, _f, _ll, _ll, _f, _f, _i, _vp, _vp, _vp],
     'dp_x0_step': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(X0Coef), _vp, _vp, _ll, _ll, _vp],

@@ -14,6 +14,9 @@
   EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, HeunDiscreteScheduler
                                scheduling_euler_discrete.py, scheduling_euler_ancestral_discrete.py, scheduling_heun_discrete.py
                                (HIP kernels dp_sigma_step, dp_sigma_scale, dp_sigma_add_noise; float64 timesteps, sample at scale sigma)
+  LMSDiscreteScheduler, KDPM2DiscreteScheduler, KDPM2AncestralDiscreteScheduler
+                               scheduling_lms_discrete.py, scheduling_k_dpm_2_discrete.py, scheduling_k_dpm_2_ancestral_discrete.py
+                               (HIP kernels dp_lms_step, dp_kdpm2_step; the multistep coefficients by the reference's quadrature)
   randn_tensor                 utils/torch_utils.py:36-77   (CPU-generator semantics kept for seed parity)
 Host-side table arithmetic (1000-entry alpha-bar table) is fp32 torch on the CPU, exactly as in the reference.
 """
@@ -1374,6 +1377,267 @@ class HeunDiscreteScheduler(_SigmaSchedulerBase):
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev)
+
+
+@dataclass
+class LMSDiscreteSchedulerOutput:
+    prev_sample: torch.Tensor
+    pred_original_sample: torch.Tensor = None
+
+
+class LMSDiscreteScheduler(_SigmaSchedulerBase):
+    """scheduling_lms_discrete.py:77-364: the linear multistep method of k-diffusion for epsilon, `v_prediction` and `sample` models,
+    with `use_karras_sigmas`.  One launch of dp_lms_step per `step`: the conversion, the derivative, the sum over up to `order`
+    derivatives and the update.  `derivatives` is the reference's list, oldest first, over at most four buffers of the scheduler's
+    own: the new derivative takes the slot of the one dropped.  `init_noise_sigma` is the training table's maximum and is not updated
+    by `set_timesteps`.
+    The coefficients are the reference's in bits: the same `scipy.integrate.quad(..., epsrel=1e-4)` over the same integrand of 0-d
+    fp32 tensors (which is not the exact integral of the polynomial: it differs around the eighth digit), each rounded to fp32 once,
+    as torch rounds a Python float that multiplies an fp32 tensor.  They are kept per (order, index) until the next `set_timesteps`;
+    the reference integrates again on every step.
+    Not carried (NotImplementedError): `trained_betas`, models that predict a variance, `order` above 4."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'use_karras_sigmas',
+                    'prediction_type')
+    _PRED = {'epsilon': ops.KDIFF_EPSILON, 'v_prediction': ops.KDIFF_V, 'sample': ops.KDIFF_SAMPLE}
+    MAX_ORDER = 4
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', trained_betas=None,
+                 use_karras_sigmas=False, prediction_type='epsilon'):
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, trained_betas=trained_betas, use_karras_sigmas=use_karras_sigmas,
+                                      prediction_type=prediction_type)
+        self._init_sigma_tables()
+        self.init_noise_sigma = torch.from_numpy(self._train_sigmas()).max()
+        self.use_karras_sigmas = use_karras_sigmas
+        self.set_timesteps(num_train_timesteps, None)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """:196-227 with the reference's numpy expressions; the derivatives and the kept coefficients reset."""
+        self.num_inference_steps = num_inference_steps
+        timesteps = np.linspace(0, self.config.num_train_timesteps - 1, num_inference_steps, dtype=float)[::-1].copy()
+        sigmas = self._train_sigmas()
+        log_sigmas = self._log(sigmas)
+        sigmas = np.interp(timesteps, np.arange(0, len(sigmas)), sigmas)
+        if self.use_karras_sigmas:
+            sigmas, timesteps = self._karras(sigmas, log_sigmas, num_inference_steps)
+        self._set_tables(timesteps, np.concatenate([sigmas, [0.0]]).astype(np.float32), device)
+        self.derivatives = []
+        self._lms = {}
+
+    def get_lms_coefficient(self, order, t, current_order):
+        """:174-194: the integral of the Lagrange basis polynomial `current_order` of `order` nodes over [sigma_t, sigma_t+1], as
+        the reference's adaptive quadrature returns it (a Python float).  tau - sigma rounds tau to fp32: the integrand is fp32."""
+        from scipy import integrate
+        sig = self._sig
+
+        def lms_derivative(tau):
+            prod = 1.0
+            for k in range(order):
+                if current_order == k:
+                    continue
+                prod *= (tau - sig[t - k]) / (sig[t - current_order] - sig[t - k])
+            return prod
+        return integrate.quad(lms_derivative, sig[t], sig[t + 1], epsrel=1e-4)[0]
+
+    def lms_coefficients(self, order, index):
+        """The `order` coefficients of table index `index`, newest derivative first, each rounded to fp32 once; integrated once."""
+        got = self._lms.get((order, index))
+        if got is None:
+            got = self._lms[(order, index)] = tuple(float(np.float32(self.get_lms_coefficient(order, index, k))) for k in range(order))
+        return got
+
+    def step_coefs(self, index, order=4, terms=None):
+        """The fp32 scalars of :302-330 as ops.lms_step names them: the first `terms` coefficients of order min(index + 1, order)."""
+        sigma = self._sig[index]
+        c = {k: float(v) for k, v in self._v_coefs(dict(sig=sigma), sigma).items()}
+        coefs = self.lms_coefficients(min(index + 1, order), index)
+        for k, v in enumerate(coefs[:len(coefs) if terms is None else terms]):
+            c['c%d' % k] = v
+        return c
+
+    def step(self, model_output, timestep, sample, order=4, return_dict=True):
+        pt = self.config.prediction_type
+        if pt not in self._PRED:
+            raise ValueError('prediction_type given as %s must be one of `epsilon`, or `v_prediction`' % pt)
+        if order > self.MAX_ORDER:
+            raise NotImplementedError('order %d: the step kernel carries at most %d derivatives' % (order, self.MAX_ORDER))
+        if order < 1:
+            raise ValueError('order must be at least 1, got %r' % (order,))
+        self._begin_step(model_output, sample)
+        i = self.index_for_timestep(timestep)
+        history = self.derivatives[::-1]                              # newest first
+        # the reference appends the new derivative and then drops the oldest of more than `order`: the kernel does not read that one
+        slot = self.derivatives.pop(0) if len(self.derivatives) + 1 > order else None
+        if not self._fits(slot, sample):
+            slot = torch.empty_like(sample, memory_format=torch.contiguous_format)
+        terms = min(i + 1, order, len(self.derivatives) + 1)          # zip() in the reference stops at the shorter list
+        prev, d, x0 = ops.lms_step(sample.contiguous(), model_output.contiguous(), self.step_coefs(i, order, terms), terms, self._PRED[pt],
+                                   history=history[:terms - 1], out=self._next_buffer(sample, sample), d_out=slot,
+                                   x0_out=self._own('_x0', sample))
+        self.derivatives.append(d)
+        if not return_dict:
+            return (prev,)
+        return LMSDiscreteSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+
+class _KDPM2Tables(_SigmaSchedulerBase):
+    """What the two KDPM2 classes share: two model calls per step but the last, so the tables are doubled (2n - 1 timesteps, 2n + 2
+    sigmas); every second timestep is the fractional time of an interpolated sigma (`sigmas_interpol`, the geometric mean of two
+    neighbours: log, lerp at 0.5 and exp in fp32 torch as the reference has them, log and exp rounded once), found by `sigma_to_t`,
+    the reference's fp32 torch search of the training table.  `sample` is the sample of the first-order call, held by reference;
+    `state_in_first_order` is `sample is None`.  One launch of dp_kdpm2_step per `step`.  `init_noise_sigma` follows
+    `set_timesteps`.  The tables keep the reference's entries that are never read (a NaN among them)."""
+    order = 2
+    _WARNS_UNSCALED = False
+    _PRED = {'epsilon': ops.KDIFF_EPSILON, 'v_prediction': ops.KDIFF_V}
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'prediction_type')
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule='linear', trained_betas=None,
+                 prediction_type='epsilon'):
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, trained_betas=trained_betas, prediction_type=prediction_type)
+        self._init_sigma_tables()
+        self.set_timesteps(num_train_timesteps, None, num_train_timesteps)
+
+    @staticmethod
+    def _tlog(t):
+        return _rounded_once(torch.log, t)
+
+    @staticmethod
+    def _geometric_mean(a, b):
+        """a.log().lerp(b.log(), 0.5).exp(): at weight 0.5 torch's lerp takes its `b - (b - a) * (1 - w)` branch."""
+        la, lb = _KDPM2Tables._tlog(a), _KDPM2Tables._tlog(b)
+        return _rounded_once(torch.exp, lb - (lb - la) * 0.5)
+
+    @staticmethod
+    def _doubled(t):
+        return torch.cat([t[:1], t[1:].repeat_interleave(2), t[-1:]])
+
+    def sigma_to_t(self, sigma):
+        """The reference's fp32 torch search: the fractional index at which log sigma lies between two neighbours of the table."""
+        log_sigmas = self._log_sigmas
+        log_sigma = self._tlog(sigma)
+        dists = log_sigma - log_sigmas[:, None]
+        low_idx = dists.ge(0).cumsum(dim=0).argmax(dim=0).clamp(max=log_sigmas.shape[0] - 2)
+        high_idx = low_idx + 1
+        low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+        w = ((low - log_sigma) / (low - high)).clamp(0, 1)
+        t = (1 - w) * low_idx + w * high_idx
+        return t.view(sigma.shape)
+
+    def set_timesteps(self, num_inference_steps, device=None, num_train_timesteps=None):
+        self.num_inference_steps = num_inference_steps
+        T = num_train_timesteps or self.config.num_train_timesteps
+        timesteps = np.linspace(0, T - 1, num_inference_steps, dtype=float)[::-1].copy()
+        sigmas = self._train_sigmas()
+        self._log_sigmas = torch.from_numpy(self._log(sigmas))
+        self.log_sigmas = self._log_sigmas.to(device)
+        sigmas = np.interp(timesteps, np.arange(0, len(sigmas)), sigmas)
+        sigmas = torch.from_numpy(np.concatenate([sigmas, [0.0]]).astype(np.float32))
+        sigmas_interpol, used = self._interpolate(sigmas, device)
+        self._interpol = self._doubled(sigmas_interpol)               # on the host, as `_sig`
+        self.sigmas_interpol = self._interpol.to(device=device)
+        timesteps = torch.from_numpy(timesteps)
+        timesteps_interpol = self.sigma_to_t(sigmas_interpol).to(dtype=timesteps.dtype)
+        interleaved = torch.stack((timesteps_interpol[used, None], timesteps[1:, None]), dim=-1).flatten()
+        self._set_tables(torch.cat([timesteps[:1], interleaved]).numpy(), self._doubled(sigmas).numpy(), device)
+        self.init_noise_sigma = self.sigmas.max()
+        self.sample = None
+
+    @property
+    def state_in_first_order(self):
+        return self.sample is None
+
+    def index_for_timestep(self, timestep):
+        """The last match in first-order state, the first otherwise: the timestep table holds equal pairs."""
+        return self._matches(timestep)[-1 if self.state_in_first_order else 0]
+
+    def scale_model_input(self, sample, timestep):
+        i = self.index_for_timestep(timestep)
+        sigma = self._sig[i] if self.state_in_first_order else self._interpol[i + self._SCALE_AT]
+        return ops.sigma_scale(sample.contiguous(), float(self._sqrt(sigma ** 2 + 1)), out=self._own('_scaled', sample))
+
+    def _step(self, model_output, timestep, sample, noise_of, return_dict):
+        pred = self._prediction()
+        self._begin_step(model_output, sample)
+        i = self.index_for_timestep(timestep)
+        first = self.state_in_first_order
+        noise = noise_of(not first)
+        c = self.step_coefs(i)
+        x, e = sample.contiguous(), model_output.contiguous()
+        if first:
+            prev = ops.kdpm2_step(x, e, c, pred, out=self._next_buffer(sample, sample))
+            self.sample = sample
+        else:
+            prev = ops.kdpm2_step(x, e, c, pred, saved=self.sample.contiguous(), noise=noise,
+                                  out=self._next_buffer(sample, sample, self.sample))
+            self.sample = None
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
+class KDPM2DiscreteScheduler(_KDPM2Tables):
+    """scheduling_k_dpm_2_discrete.py:53-340: DPM-Solver-2 in the form of Algorithm 2 of Karras et al. (2022) without churn, for
+    epsilon and `v_prediction` models.  The first call of a pair steps to the interpolated sigma, the second from the saved sample
+    to the next sigma with the derivative taken there.  `sigmas_interpol[0]` is NaN, as the reference's is (a lerp towards log 0);
+    it is never read.
+    Not carried: `trained_betas`, models that predict a variance (NotImplementedError); `sample` models (the reference's
+    NotImplementedError from `step`)."""
+    _SCALE_AT = 0
+
+    def _interpolate(self, sigmas, device):
+        """:180-201: (sigmas_interpol, the entries of it whose times are interleaved into `timesteps`)."""
+        return self._geometric_mean(sigmas, sigmas.roll(1)), slice(1, -1)
+
+    def step_coefs(self, index):
+        """The fp32 scalars of :254-305 as ops.kdpm2_step names them, for the state the scheduler is in."""
+        if self.state_in_first_order:
+            sigma, sigma_interpol = self._sig[index], self._interpol[index + 1]
+            sigma_input, dt = sigma * (0 + 1), sigma_interpol - sigma * (0 + 1)
+        else:
+            sigma, sigma_interpol, sigma_next = self._sig[index - 1], self._interpol[index], self._sig[index]
+            sigma_input, dt = sigma_interpol, sigma_next - sigma * (0 + 1)
+        return {k: float(v) for k, v in self._v_coefs(dict(sig=sigma_input, dt=dt), sigma_input).items()}
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        return self._step(model_output, timestep, sample, lambda needed: None, return_dict)
+
+
+class KDPM2AncestralDiscreteScheduler(_KDPM2Tables):
+    """scheduling_k_dpm_2_ancestral_discrete.py:54-358: KDPM2 with ancestral noise, for epsilon and `v_prediction` models.  The
+    interpolated sigma lies between sigma and `sigmas_down`; the second call of a pair steps from the saved sample to sigma_down and
+    adds noise * sigma_up.  The noise is drawn on every call, as the reference draws it, and uploaded for the second call of a pair
+    only.  The timestep table holds equal or nearly equal pairs, so the lookup goes by the state.
+    Not carried: `trained_betas`, models that predict a variance (NotImplementedError); `sample` models (the reference's
+    NotImplementedError from `step`)."""
+    _SCALE_AT = -1
+
+    def _interpolate(self, sigmas, device):
+        """:181-210: sigmas_up and sigmas_down beside sigmas_interpol."""
+        sigmas_next = sigmas.roll(-1)
+        sigmas_next[-1] = 0.0
+        sigmas_up = self._sqrt(sigmas_next ** 2 * (sigmas ** 2 - sigmas_next ** 2) / sigmas ** 2)
+        sigmas_down = self._sqrt(sigmas_next ** 2 - sigmas_up ** 2)
+        sigmas_down[-1] = 0.0
+        sigmas_interpol = self._geometric_mean(sigmas, sigmas_down)
+        sigmas_interpol[-2:] = 0.0
+        self._up, self._down = self._doubled(sigmas_up), self._doubled(sigmas_down)
+        self.sigmas_up, self.sigmas_down = self._up.to(device=device), self._down.to(device=device)
+        return sigmas_interpol, slice(None, -2)
+
+    def step_coefs(self, index):
+        """The fp32 scalars of :266-324 as ops.kdpm2_step names them, for the state the scheduler is in."""
+        if self.state_in_first_order:
+            sigma, sigma_interpol = self._sig[index], self._interpol[index]
+            c = dict(sig=sigma * (0 + 1), dt=sigma_interpol - sigma * (0 + 1))
+        else:
+            sigma, sigma_interpol = self._sig[index - 1], self._interpol[index - 1]
+            c = dict(sig=sigma_interpol, dt=self._down[index - 1] - sigma * (0 + 1), sigma_up=self._up[index - 1])
+        return {k: float(v) for k, v in self._v_coefs(c, c['sig']).items()}
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True):
+        return self._step(model_output, timestep, sample, lambda needed: self._draw(model_output, generator, needed), return_dict)
 
 
 @dataclass

@@ -2372,6 +2372,68 @@ def sigma_add_noise(x0, noise, sigma, out=None):
     return out
 
 
+KDIFF_MAX_BLOCKS = 4096              # DP_KDIFF_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
+KDPM2_COEF = ('sig', 'c_out', 'c_den', 'dt', 'sigma_up')
+LMS_COEF = ('sig', 'c_out', 'c_den', 'c0', 'c1', 'c2', 'c3')
+KDIFF_EPSILON, KDIFF_V, KDIFF_SAMPLE = range(3)                              # DP_KDIFF_* (include/dp_hip.h): the values of `pred`
+KDPM2_FIRST, KDPM2_SECOND, KDPM2_SECOND_NOISE = range(3)                     # the shape of a call: which of `saved` / `noise` it is handed
+# what the library instantiates: (shape, pred) of dp_kdpm2_step, (order, pred) of dp_lms_step
+KDPM2_INSTANCES = tuple((s, p) for s in range(3) for p in (KDIFF_EPSILON, KDIFF_V))
+LMS_INSTANCES = tuple((o, p) for o in range(1, 5) for p in range(3))
+
+
+def _kdiff_like(x, name, *ts):
+    for t in ts:
+        assert t.dtype == _f32 and t.is_contiguous() and t.numel() == x.numel() and t.device == x.device, \
+            name + ': contiguous fp32 tensors of one size on one device'
+
+
+def kdpm2_step(x, e, coef, pred=KDIFF_EPSILON, saved=None, noise=None, out=None):
+    """One call of KDPM2DiscreteScheduler / KDPM2AncestralDiscreteScheduler (dp_kdpm2_step, csrc/kdiff.hip) over flat fp32 data.
+    `coef`: the host's fp32 scalars by name (KDPM2_COEF; one the call does not read may be left out).  x0 = x - sig e
+    (KDIFF_EPSILON) | e c_out + x / c_den (KDIFF_V); d = (x - x0) / sig; out = (saved if given else x) + d dt, + noise sigma_up
+    with `noise` (which needs `saved`).  `out` may be `x` or `saved`; no other buffer may be shared.  Returns out."""
+    assert pred in (KDIFF_EPSILON, KDIFF_V), pred
+    assert noise is None or saved is not None, 'kdpm2_step: noise belongs to the second-order call'
+    assert x.dtype == _f32 and x.is_contiguous()
+    ins = [t for t in (e, noise) if t is not None]
+    _kdiff_like(x, 'kdpm2_step', *(ins + ([saved] if saved is not None else [])))
+    if out is None:
+        out = torch.empty_like(x)
+    _kdiff_like(x, 'kdpm2_step', out)
+    assert out.data_ptr() not in [t.data_ptr() for t in ins]
+    unknown = set(coef) - set(KDPM2_COEF)
+    assert not unknown, unknown
+    c = L.Kdpm2Coef(**{k: float(v) for k, v in coef.items()})
+    L.check(_lib().dp_kdpm2_step(_p(x), _p(e), _p(saved), _p(noise), int(pred), C.byref(c), _p(out), x.numel(), _stream()), 'dp_kdpm2_step')
+    return out
+
+
+def lms_step(x, e, coef, order, pred=KDIFF_EPSILON, history=(), out=None, d_out=None, x0_out=None):
+    """One call of LMSDiscreteScheduler (dp_lms_step, csrc/kdiff.hip) over flat fp32 data.  `coef`: sig, c_out / c_den (KDIFF_V) and
+    c0 .. c{order-1} by name (LMS_COEF); `history`: the previous derivatives, newest first, at least order - 1 of them (the rest is
+    not read).  x0 = x - sig e | e c_out + x / c_den | e (KDIFF_SAMPLE); d = (x - x0) / sig; out = x + (c0 d + c1 history[0] + ...).
+    `out` may be `x`; d_out and x0_out share no buffer with anything.  Returns (out, d_out, x0_out)."""
+    assert order in (1, 2, 3, 4) and pred in (KDIFF_EPSILON, KDIFF_V, KDIFF_SAMPLE), (order, pred)
+    assert x.dtype == _f32 and x.is_contiguous()
+    history = list(history)[:order - 1]
+    assert len(history) == order - 1, 'lms_step: order %d needs %d previous derivatives' % (order, order - 1)
+    ins = [e] + history
+    _kdiff_like(x, 'lms_step', *ins)
+    out, d_out, x0_out = (torch.empty_like(x) if t is None else t for t in (out, d_out, x0_out))
+    _kdiff_like(x, 'lms_step', out, d_out, x0_out)
+    assert out.data_ptr() not in [t.data_ptr() for t in ins]
+    assert d_out.data_ptr() not in [t.data_ptr() for t in ins + [x, out]]
+    assert x0_out.data_ptr() not in [t.data_ptr() for t in ins + [x, out, d_out]]
+    unknown = set(coef) - set(LMS_COEF)
+    assert not unknown, unknown
+    c = L.LmsCoef(**{k: float(v) for k, v in coef.items()})
+    d = history + [None] * (3 - len(history))
+    L.check(_lib().dp_lms_step(_p(x), _p(e), _p(d[0]), _p(d[1]), _p(d[2]), int(order), int(pred), C.byref(c), _p(out), _p(d_out),
+                               _p(x0_out), x.numel(), _stream()), 'dp_lms_step')
+    return out, d_out, x0_out
+
+
 UNIPC_MAX_BLOCKS = 4096             # DP_UNIPC_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, grid-stride beyond
 UNIPC_COEF = ('sigma_s', 'alpha_s', 'c_cx', 'c_c0', 'c_cB', 'c_rk1', 'c_rk2', 'c_rho1', 'c_rho2', 'c_rho_last',
               'p_cx', 'p_c0', 'p_cB', 'p_rk1', 'p_rk2', 'p_rho1', 'p_rho2')

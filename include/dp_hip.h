@@ -523,7 +523,7 @@ int dp_ddpm_step(const float* x, const float* eps, const float* vnoise, float sq
                  float c_xt, float sigma, int clip, float clip_range, float* out, long long n, void* stream);
 
 /* ---- The head / body / tail access rule of the elementwise step launchers below (dp_denoise_step, dp_cfg_denoise_step,
- * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_repaint_step, dp_repaint_undo, dp_sigma_step and its two companions, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
+ * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_repaint_step, dp_repaint_undo, dp_sigma_step and its two companions, dp_kdpm2_step, dp_lms_step, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
  * When every pointer in use (a NULL or unread one does not count) shares one 4-byte-aligned phase modulo 16, a scalar head of
  * 0 .. 3 elements brings all of them to 16 bytes: the n4 = (n - head) / 4 groups after it take 16-byte accesses, the head and the
  * n - head - 4 n4 tail elements 4-byte ones.  Otherwise every access is 4 bytes (head = n).  Any n: long long indexing, one lane
@@ -744,6 +744,48 @@ int dp_sigma_step(const float* x, const float* e, const float* z, const float* d
                   const dp_sigma_coef* coef, float* x_next, float* aux_out, long long n, void* stream);
 int dp_sigma_scale(const float* x, float c, float* out, long long n, void* stream);
 int dp_sigma_add_noise(const float* x0, const float* z, const float* sigma, long long B, long long per, float* out, void* stream);
+
+/* The step kernels of the rest of the sigma-space family (csrc/kdiff.hip; diffusers/schedulers/scheduling_k_dpm_2_discrete.py
+ * :252-305, scheduling_k_dpm_2_ancestral_discrete.py:264-324, scheduling_lms_discrete.py:299-330) over n fp32 elements, one pass each,
+ * in the reference's operation order.  x the sample, e the model output.
+ *   x0:  DP_KDIFF_EPSILON  x - sig * e;   DP_KDIFF_V  e * c_out + x / c_den;   DP_KDIFF_SAMPLE (dp_lms_step only)  e
+ * dp_kdpm2_step: one call of KDPM2DiscreteScheduler or KDPM2AncestralDiscreteScheduler.  xs: the sample the first-order call was
+ * handed, NULL in first-order state; z: the noise, given only for the ancestral class's second-order call.
+ *   d = (x - x0) / sig;  r = (xs ? xs : x) + d * dt;  x_next = z ? r + z * sigma_up : r
+ * Three shapes (first, second, second + noise) x two types: six instantiations.  It writes no derivative and no x0: 4 streams read at
+ * most, 1 written.  sig = sigma_hat in first-order state, sigma_interpol in second-order state; c_out = -sig / (sig^2 + 1) ** 0.5 and
+ * c_den = sig^2 + 1; dt = sigma_interpol - sigma_hat, then sigma_next (ancestral: sigma_down) - sigma_hat.
+ * Aliases: `x_next` may be `x` itself or `xs` itself.  Any other overlap, a null x, e, coef or x_next, z without xs and a type outside
+ * 0 .. 1 are hipErrorInvalidValue: nothing is launched.
+ * dp_lms_step: one linear-multistep call.  d1 .. d3: the previous derivatives, newest first; those beyond `order` are not read and may
+ * be NULL.
+ *   d = (x - x0) / sig;  acc = c0 * d;  acc = acc + c1 * d1;  ... (`order` terms, in that order);  x_next = x + acc
+ *   d_new = d;  x0_out = x0
+ * Orders 1 .. 4 x three types: twelve instantiations.  c0 .. c3: the host's integrals of the Lagrange basis over [sigma, sigma_next],
+ * each rounded to fp32 once.
+ * Aliases: `x_next` may be `x` itself.  d_new and x0_out overlap nothing that the call reads, nor each other, nor x_next.  Any other
+ * overlap, a null pointer that the order reads or writes, an order outside 1 .. 4 and a type outside 0 .. 2 are
+ * hipErrorInvalidValue: nothing is launched.
+ * Both: every operation rounded separately, true divisions, n <= 0 is a no-op.
+ * Accesses: the head / body / tail rule above, at most DP_KDIFF_MAX_BLOCKS blocks. */
+#define DP_KDIFF_MAX_BLOCKS 4096
+#define DP_KDIFF_EPSILON 0
+#define DP_KDIFF_V 1
+#define DP_KDIFF_SAMPLE 2
+typedef struct dp_kdpm2_coef {
+    float sig;                          /* the sigma of the conversion and of the derivative */
+    float c_out, c_den;                 /* the v-conversion (DP_KDIFF_V only) */
+    float dt, sigma_up;                 /* the update; sigma_up: with z only */
+} dp_kdpm2_coef;
+typedef struct dp_lms_coef {
+    float sig;                          /* the sigma of the conversion and of the derivative */
+    float c_out, c_den;                 /* the v-conversion (DP_KDIFF_V only) */
+    float c0, c1, c2, c3;               /* the multistep coefficients, newest derivative first; those beyond `order` are not read */
+} dp_lms_coef;
+int dp_kdpm2_step(const float* x, const float* e, const float* xs, const float* z, int pred, const dp_kdpm2_coef* coef,
+                  float* x_next, long long n, void* stream);
+int dp_lms_step(const float* x, const float* e, const float* d1, const float* d2, const float* d3, int order, int pred,
+                const dp_lms_coef* coef, float* x_next, float* d_new, float* x0_out, long long n, void* stream);
 
 /* x0 forming, dynamic thresholding and the DDPM / DDIM update for epsilon, sample and v-prediction models (csrc/threshold.hip;
  * diffusers/schedulers/scheduling_ddpm.py:278-310, :355-401, scheduling_ddim.py:205-237, :334-385) over B images of n fp32 elements.
