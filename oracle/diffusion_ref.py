@@ -122,13 +122,15 @@ def to_image(x):
     return (x / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1)
 
 
-def taylor_sweep(P, cfg, clean, noise, steps, thr=None, loss_kind='mse', on_step=None, accumulate_breaking_step=True):
+def taylor_sweep(P, cfg, clean, noise, steps, thr=None, loss_kind='mse', on_step=None, accumulate_breaking_step=True,
+                 softmax_dtype=torch.float32):
     """ddpm_prune.py:94-106.  P: dict of leaf tensors with requires_grad; grads accumulate into .grad.
 
     thr=None -> plain Taylor (all `steps`); thr=x -> Diff-Pruning early exit; the breaking step IS
     accumulated (backward happens before the threshold test, ddpm_prune.py:102-106).
     accumulate_breaking_step=False -> the ddpm_exp flavour (ddpm_exp/prune.py:249-256): threshold test first, the
     breaking step is NOT accumulated (pinned by tests/golden/ddpm_original.json 'sweep').
+    softmax_dtype: unet_ref.attention_block (torch.float64 for an fp64 run that serves as a high-precision reference).
     Returns the list of per-step losses (python floats)."""
     acp = alphas_cumprod()
     for p in P.values():
@@ -139,7 +141,7 @@ def taylor_sweep(P, cfg, clean, noise, steps, thr=None, loss_kind='mse', on_step
     for k in range(steps):
         t = torch.full((B,), k, dtype=torch.long)
         noisy = add_noise(acp, clean, noise, t)
-        out = unet_forward(P, cfg, noisy, t)
+        out = unet_forward(P, cfg, noisy, t, softmax_dtype=softmax_dtype)
         if loss_kind == 'mse':
             loss = F.mse_loss(out, noise)
         else:                                   # ddpm_exp/functions/losses.py:15, ddpm_train.py:459

@@ -65,7 +65,7 @@ def resnet_block(P, pre, x, temb, groups, eps, out_scale, drop=None):
     return (x + h) / out_scale
 
 
-def attention_block(P, pre, x, groups, eps, scale, rescale, heads=1, drop=None):
+def attention_block(P, pre, x, groups, eps, scale, rescale, heads=1, drop=None, softmax_dtype=torch.float32):
     """attention_processor.py:415-470 (AttnProcessor; head_to_batch_dim / batch_to_head_dim :283-305), residual_connection=True.
 
     `scale` and `heads` are module attributes fixed at construction (dim_head ** -0.5 with dim_head = attention_head_dim
@@ -87,7 +87,9 @@ def attention_block(P, pre, x, groups, eps, scale, rescale, heads=1, drop=None):
         q, k, v = to_batch(q), to_batch(k), to_batch(v)
     s = torch.baddbmm(torch.empty(q.shape[0], q.shape[1], k.shape[1], dtype=q.dtype, device=q.device), q,
                       k.transpose(-1, -2), beta=0, alpha=scale)
-    p = s.float().softmax(dim=-1).to(q.dtype)
+    # upcast_softmax: the reference casts the scores to fp32 whatever the model's dtype (softmax_dtype = torch.float32, which the
+    # fp64 fixtures of the reference pin); an fp64 run that is to be a high-precision reference passes torch.float64
+    p = s.to(softmax_dtype).softmax(dim=-1).to(q.dtype)
     h = torch.bmm(p, v)
     if heads > 1:
         h = h.reshape(B, heads, T, h.shape[-1]).permute(0, 2, 1, 3).reshape(B, T, heads * h.shape[-1])
@@ -122,8 +124,9 @@ def attn_heads_for(cfg, channels):
     return channels // hd if hd is not None else 1
 
 
-def unet_forward(P, cfg, sample, timesteps, drop=None):
-    """unet_2d.py:219-316.  P: flat parameter dict, cfg: Diffusers UNet2DModel config dict.  drop: see resnet_block."""
+def unet_forward(P, cfg, sample, timesteps, drop=None, softmax_dtype=torch.float32):
+    """unet_2d.py:219-316.  P: flat parameter dict, cfg: Diffusers UNet2DModel config dict.  drop: see resnet_block;
+    softmax_dtype: see attention_block."""
     boc = list(cfg['block_out_channels'])
     groups, eps = cfg['norm_num_groups'], cfg['norm_eps']
     L = cfg['layers_per_block']
@@ -147,7 +150,7 @@ def unet_forward(P, cfg, sample, timesteps, drop=None):
             x = resnet_block(P, '%s.resnets.%d' % (pre, j), x, emb, groups, eps, 1.0, drop)
             if bt == 'AttnDownBlock2D':
                 x = attention_block(P, '%s.attentions.%d' % (pre, j), x, groups, eps,
-                                    attn_scale_for(cfg, boc[i]), 1.0, attn_heads_for(cfg, boc[i]), drop)
+                                    attn_scale_for(cfg, boc[i]), 1.0, attn_heads_for(cfg, boc[i]), drop, softmax_dtype)
             skips.append(x)
         if i != nb - 1:
             x = downsample(P, pre + '.downsamplers.0', x, cfg['downsample_padding'])
@@ -157,7 +160,7 @@ def unet_forward(P, cfg, sample, timesteps, drop=None):
     x = resnet_block(P, 'mid_block.resnets.0', x, emb, groups, eps, msf, drop)
     if cfg.get('add_attention', True):
         x = attention_block(P, 'mid_block.attentions.0', x, groups, eps, attn_scale_for(cfg, boc[-1]), msf,
-                            attn_heads_for(cfg, boc[-1]), drop)
+                            attn_heads_for(cfg, boc[-1]), drop, softmax_dtype)
     x = resnet_block(P, 'mid_block.resnets.1', x, emb, groups, eps, msf, drop)
 
     rev = list(reversed(boc))
@@ -168,7 +171,7 @@ def unet_forward(P, cfg, sample, timesteps, drop=None):
             x = resnet_block(P, '%s.resnets.%d' % (pre, j), x, emb, groups, eps, 1.0, drop)
             if bt == 'AttnUpBlock2D':
                 x = attention_block(P, '%s.attentions.%d' % (pre, j), x, groups, eps,
-                                    attn_scale_for(cfg, rev[i]), 1.0, attn_heads_for(cfg, rev[i]), drop)
+                                    attn_scale_for(cfg, rev[i]), 1.0, attn_heads_for(cfg, rev[i]), drop, softmax_dtype)
         if i != nb - 1:
             x = upsample(P, pre + '.upsamplers.0', x)
 
