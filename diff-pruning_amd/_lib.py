@@ -113,6 +113,14 @@ class DpmSolverCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sigma_s', 'alpha_s', 'kx', 'k0', 'k1', 'k2', 'ir0', 'ir1', 'q', 'iq')]
 
 
+class DeisCoef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'kx', 'k0', 'at', 'as0', 'c1', 'c2', 'c3')]
+
+
+class DpmSingleCoef(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'kx', 'k0', 'k1', 'k2', 'ir0', 'ir1', 'r0', 'r1', 'dr')]
+
+
 class PndmCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('sa', 'sb', 'sc', 'd', 'den', 'c6', 'c3', 'c24')]
 
@@ -253,6 +261,8 @@ SIGNATURES = {
     'dp_x0_abs_quantile': [_vp, _vp, _ll, _ll, _i, _f, _f, _ll, _ll, _f, _f, _i, _vp, _vp, _vp],
     'dp_x0_step': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(X0Coef), _vp, _vp, _ll, _ll, _vp],
     'dp_x0_threshold_step': [_vp, _vp, _vp, _i, _i, _i, C.POINTER(X0Coef), _ll, _ll, _f, _f, _vp, _vp, _vp, _ll, _ll, _vp],
+    'dp_deis_step': [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(DeisCoef), _vp, _vp, _ll, _ll, _vp],
+    'dp_dpm_single_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(DpmSingleCoef), _vp, _vp, _ll, _ll, _vp],
     'dp_dropout_apply': [_vp, _ll, _vp, _ll, _i, _ll, _dr, _vp],
     'dp_dropout_mask': [_vp, _ll, _ll, _dr, _vp],
     'dp_layernorm_fwd': [_vp, _ll, _vp, _vp, _i, _i, _i, _f, _vp, _ll, _vp, _vp],

@@ -730,6 +730,275 @@ class UniPCMultistepScheduler(_MultistepBase):
         return SchedulerOutput(prev_sample=prev)
 
 
+class _TreatedSolverBase(_MultistepBase):
+    """What DEISMultistepScheduler and DPMSolverSinglestepScheduler share beyond _MultistepBase: the three model types and dynamic
+    thresholding, whose per-image s is one launch of the exact quantile (ops.x0_abs_quantile) ahead of the step's own."""
+
+    def _check_common(self, trained_betas, solver_order, prediction_type):
+        if trained_betas is not None:
+            raise NotImplementedError('trained_betas is not on the hot path')
+        if prediction_type not in self._PREDICTION_TYPES:
+            raise ValueError('prediction_type given as %s must be one of `epsilon`, `sample`, or `v_prediction` for the %s.'
+                             % (prediction_type, type(self).__name__))
+        if int(solver_order) < 1:
+            raise ValueError('solver_order must be at least 1')
+        if int(solver_order) > 3:
+            raise NotImplementedError('solver_order %d: the kernel carries orders 1 to 3' % solver_order)
+
+    def _begin_solver_step(self, model_output, timestep, sample):
+        begun = self._begin_step(timestep)
+        if model_output.shape[1] != sample.shape[1]:
+            raise NotImplementedError('a model output of %d channels for a sample of %d (a predicted variance) is not part of this path'
+                                      % (model_output.shape[1], sample.shape[1]))
+        return begun
+
+    def _stats(self, sample, model_output, coef):
+        """The [B, 4] table of the thresholded x0's quantile: one launch, nothing read back."""
+        return ops.x0_abs_quantile(sample, model_output, ops.X0_PRED[self.config.prediction_type], coef['sa'], coef['sb'],
+                                   self.config.dynamic_thresholding_ratio, self.config.sample_max_value)
+
+
+def _log_once(v):
+    return _rounded_once(torch.log, v)
+
+
+def _exp_once(v):
+    return _rounded_once(torch.exp, v)
+
+
+class DEISMultistepScheduler(_TreatedSolverBase):
+    """scheduling_deis_multistep.py:58-513, the log-rho multistep DEIS of orders 1 .. 3 for epsilon, `sample` and `v_prediction`
+    models, with dynamic thresholding (`thresholding`, `dynamic_thresholding_ratio`, `sample_max_value`; with the default
+    sample_max_value = 1.0 every s is 1 and the option is a clip to [-1, 1]).  The tables and every per-step scalar are 0-d fp32 torch
+    arithmetic on the CPU in the reference's operation order (:298-303, :329-345, :371-401), with sqrt, log and exp correctly rounded
+    (_rounded_once) -- the log of the log-rho coefficients too, which the reference takes with numpy's fp32 log.  The per-element work
+    of a step -- convert_model_output, which always converts to x0 and back to epsilon, and the update -- is ONE launch of dp_deis_step
+    (ops.deis_step); a thresholded step is the quantile's launch (ops.x0_abs_quantile) and that one.  `step` reads nothing back.
+    Not carried (NotImplementedError): `trained_betas`, solver_order above 3, models that predict a variance."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'solver_order',
+                    'prediction_type', 'thresholding', 'dynamic_thresholding_ratio', 'sample_max_value', 'algorithm_type',
+                    'solver_type', 'lower_order_final')
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', trained_betas=None,
+                 solver_order=2, prediction_type='epsilon', thresholding=False, dynamic_thresholding_ratio=0.995,
+                 sample_max_value=1.0, algorithm_type='deis', solver_type='logrho', lower_order_final=True):
+        self._check_common(trained_betas, solver_order, prediction_type)
+        if algorithm_type in ('dpmsolver', 'dpmsolver++'):            # :155-165: the two rewrites of register_to_config
+            algorithm_type = 'deis'
+        if algorithm_type != 'deis':
+            raise NotImplementedError('algorithm_type %s is not implemented' % algorithm_type)
+        if solver_type in ('midpoint', 'heun', 'bh1', 'bh2'):
+            solver_type = 'logrho'
+        if solver_type != 'logrho':
+            raise NotImplementedError('solver_type %s is not implemented' % solver_type)
+        self.config = SimpleNamespace(
+            num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+            trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
+            dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value,
+            algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final)
+        self._init_solver_tables(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self.num_inference_steps = None
+        self._set_list(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """:174-203: the rounded linspace, duplicates removed in order of appearance, the history reset."""
+        self._set_unique(self._rounded_linspace(self.config.num_train_timesteps - 1, num_inference_steps), device)
+
+    def step_coefs(self, order, timestep, prev_timestep, s1=None, s2=None):
+        """The fp32 scalars of one update as ops.deis_step names them, formed as :298-303, :331-343 and :373-399 form them.
+        `timestep` = s0, the step's own; s1 / s2: the two timesteps before it (orders 2 / 3)."""
+        t, s0 = prev_timestep, timestep
+        alpha_t, alpha_s0 = self.alpha_t[t], self.alpha_t[s0]
+        sigma_t, sigma_s0 = self.sigma_t[t], self.sigma_t[s0]
+        c = dict(sa=alpha_s0, sb=sigma_s0)
+        log = _log_once
+        if order == 1:
+            h = self.lambda_t[t] - self.lambda_t[s0]
+            c['kx'] = alpha_t / alpha_s0
+            c['k0'] = sigma_t * (_exp_once(h) - 1.0)
+        elif order == 2:
+            rho_t, rho_s0, rho_s1 = sigma_t / alpha_t, sigma_s0 / alpha_s0, self.sigma_t[s1] / self.alpha_t[s1]
+
+            def ind_fn(t, b, c):
+                return t * (-log(c) + log(t) - 1) / (log(b) - log(c))
+            c['c1'] = ind_fn(rho_t, rho_s0, rho_s1) - ind_fn(rho_s0, rho_s0, rho_s1)
+            c['c2'] = ind_fn(rho_t, rho_s1, rho_s0) - ind_fn(rho_s0, rho_s1, rho_s0)
+        else:
+            rho_t, rho_s0 = sigma_t / alpha_t, sigma_s0 / alpha_s0
+            rho_s1, rho_s2 = self.sigma_t[s1] / self.alpha_t[s1], self.sigma_t[s2] / self.alpha_t[s2]
+
+            def ind_fn(t, b, c, d):
+                numerator = t * (log(c) * (log(d) - log(t) + 1) - log(d) * log(t) + log(d) + log(t) ** 2 - 2 * log(t) + 2)
+                denominator = (log(b) - log(c)) * (log(b) - log(d))
+                return numerator / denominator
+            c['c1'] = ind_fn(rho_t, rho_s0, rho_s1, rho_s2) - ind_fn(rho_s0, rho_s0, rho_s1, rho_s2)
+            c['c2'] = ind_fn(rho_t, rho_s1, rho_s2, rho_s0) - ind_fn(rho_s0, rho_s1, rho_s2, rho_s0)
+            c['c3'] = ind_fn(rho_t, rho_s2, rho_s0, rho_s1) - ind_fn(rho_s0, rho_s2, rho_s0, rho_s1)
+        if order >= 2:
+            c.update(at=alpha_t, as0=alpha_s0)
+        return {k: float(v) for k, v in c.items()}
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        """:407-473.  The order is the reference's choice (solver_order, the lower_order_nums warm-up, lower_order_final /
+        lower_order_second below 15 steps); exactly one launch, two with thresholding, nothing read back."""
+        ts, last, t, i, prev_t = self._begin_solver_step(model_output, timestep, sample)
+        final = i == last and self.config.lower_order_final and len(ts) < 15
+        second = i == last - 1 and self.config.lower_order_final and len(ts) < 15
+        so = self.config.solver_order
+        if so == 1 or self.lower_order_nums < 1 or final:
+            order = 1
+        elif so == 2 or self.lower_order_nums < 2 or second:
+            order = 2
+        else:
+            order = 3
+        coef = self.step_coefs(order, t, prev_t, ts[i - 1] if order >= 2 else None, ts[i - 2] if order == 3 else None)
+        sample, model_output = sample.contiguous(), model_output.contiguous()
+        hist = self.model_outputs
+        prev, m0 = ops.deis_step(sample, model_output, coef, order=order, pred=ops.X0_PRED[self.config.prediction_type],
+                                 m1=hist[-1] if order >= 2 else None, m2=hist[-2] if order == 3 else None,
+                                 stats=self._stats(sample, model_output, coef) if self.config.thresholding else None,
+                                 m0_out=self._oldest_buffer(sample))
+        self._push_output(m0)
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
+class DPMSolverSinglestepScheduler(_TreatedSolverBase):
+    """scheduling_dpmsolver_singlestep.py:60-658, the singlestep DPM-Solver / DPM-Solver++ of orders 1 .. 3 (midpoint / heun) for
+    epsilon, `sample` and `v_prediction` models, with dynamic thresholding on the dpmsolver++ branch (the reference applies none under
+    `dpmsolver`, and neither does this class).  A solver step of order k spans k model evaluations: the first is a first-order step
+    from the sample it is handed, which the scheduler keeps (`self.sample`, a reference -- no copy launch; every `step` writes into a
+    buffer of its own, so nothing lands in it); the k-th restarts from that saved sample with the k converted outputs.  The tables and
+    every per-step scalar are 0-d fp32 torch arithmetic on the CPU in the reference's operation order (:379-386, :414-446, :475-518),
+    with sqrt, log and exp correctly rounded (_rounded_once); the per-element work of a step is ONE launch of dp_dpm_single_step
+    (ops.dpm_single_step), two with thresholding.  `step` reads nothing back.
+    A reference oddity, reproduced: `step` takes its order from `order_list`, which __init__ builds once for num_train_timesteps steps
+    (:195, :599), and not from `orders`, which set_timesteps builds for the steps asked for.  With solver_order = 3 and 9 steps the
+    last step is therefore a third-order one, where `orders` says 1.
+    Unlike the multistep classes the reference does not remove duplicate timesteps here, and its `step` then fails on the duplicate;
+    set_timesteps raises ValueError for such a step count.
+    Not carried (NotImplementedError): `trained_betas`, solver_order above 3, models that predict a variance."""
+    _CONFIG_KEYS = ('num_train_timesteps', 'beta_start', 'beta_end', 'beta_schedule', 'trained_betas', 'solver_order',
+                    'prediction_type', 'thresholding', 'dynamic_thresholding_ratio', 'sample_max_value', 'algorithm_type',
+                    'solver_type', 'lower_order_final', 'lambda_min_clipped', 'variance_type')
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule='linear', trained_betas=None,
+                 solver_order=2, prediction_type='epsilon', thresholding=False, dynamic_thresholding_ratio=0.995,
+                 sample_max_value=1.0, algorithm_type='dpmsolver++', solver_type='midpoint', lower_order_final=True,
+                 lambda_min_clipped=-float('inf'), variance_type=None):
+        self._check_common(trained_betas, solver_order, prediction_type)
+        if variance_type in ('learned', 'learned_range'):
+            raise NotImplementedError('learned-variance models are not part of this path')
+        if algorithm_type == 'deis':                                  # :178-187: the two rewrites of register_to_config
+            algorithm_type = 'dpmsolver++'
+        if algorithm_type not in ('dpmsolver', 'dpmsolver++'):
+            raise NotImplementedError('algorithm_type %s is not implemented' % algorithm_type)
+        if solver_type in ('logrho', 'bh1', 'bh2'):
+            solver_type = 'midpoint'
+        if solver_type not in ('midpoint', 'heun'):
+            raise NotImplementedError('solver_type %s is not implemented' % solver_type)
+        self.config = SimpleNamespace(
+            num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+            trained_betas=trained_betas, solver_order=solver_order, prediction_type=prediction_type, thresholding=thresholding,
+            dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value,
+            algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final,
+            lambda_min_clipped=lambda_min_clipped, variance_type=variance_type)
+        self._init_solver_tables(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self.num_inference_steps = None
+        self._set_list(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
+        self.order_list = self.get_order_list(num_train_timesteps)
+
+    def _reset_history(self):
+        self.sample = None
+
+    def get_order_list(self, num_inference_steps):
+        """:197-229: the solver order at each step."""
+        steps, order = num_inference_steps, self.config.solver_order
+        if not self.config.lower_order_final:
+            return list(range(1, order + 1)) * (steps // order)
+        if order == 3:
+            if steps % 3 == 0:
+                return [1, 2, 3] * (steps // 3 - 1) + [1, 2] + [1]
+            return [1, 2, 3] * (steps // 3) + [1, 2][:steps % 3]
+        if order == 2:
+            return [1, 2] * (steps // 2) + [1] * (steps % 2)
+        return [1] * steps
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """:231-254: the lambda_min_clipped search and the rounded linspace; duplicates are NOT removed (see the class), `orders`."""
+        clipped_idx = int(torch.searchsorted(torch.flip(self.lambda_t, [0]), self.config.lambda_min_clipped))
+        ts = self._rounded_linspace(self.config.num_train_timesteps - 1 - clipped_idx, num_inference_steps)
+        if len(set(ts.tolist())) != len(ts):
+            raise ValueError('%d inference steps give a timestep table with duplicates, which the singlestep solver cannot step through'
+                             % num_inference_steps)
+        self._set_list(ts, device)
+        self.num_inference_steps = num_inference_steps
+        self.orders = self.get_order_list(num_inference_steps)
+
+    def step_coefs(self, order, timestep, prev_timestep, s1=None, s2=None):
+        """The fp32 scalars of one update as ops.dpm_single_step names them, formed as :379-386, :414-446 and :475-518 form them.
+        `timestep` = s0, the step's own; s1 / s2: the two timesteps before it (orders 2 / 3).  The update starts at the oldest."""
+        t, s0 = prev_timestep, timestep
+        plus = self.config.algorithm_type == 'dpmsolver++'
+        heun = self.config.solver_type == 'heun'
+        base = (s0, s1, s2)[order - 1]
+        lambda_t, lambda_b = self.lambda_t[t], self.lambda_t[base]
+        alpha_t, sigma_t = self.alpha_t[t], self.sigma_t[t]
+        h = lambda_t - lambda_b
+        exp = _exp_once
+        c = dict(sa=self.alpha_t[s0], sb=self.sigma_t[s0])
+        if plus:
+            c['kx'] = sigma_t / self.sigma_t[base]
+            c['k0'] = alpha_t * (exp(-h) - 1.0)
+        else:
+            c['kx'] = alpha_t / self.alpha_t[base]
+            c['k0'] = sigma_t * (exp(h) - 1.0)
+        if order >= 2:
+            r0 = (self.lambda_t[s0] - lambda_b) / h
+            c['ir0'] = 1.0 / r0
+            if order == 2 and not heun:
+                c['k1'] = 0.5 * c['k0']
+            elif plus:                                                # the reference ADDS this term: k1 is its negative
+                c['k1'] = -(alpha_t * ((exp(-h) - 1.0) / h + 1.0))
+            else:
+                c['k1'] = sigma_t * ((exp(h) - 1.0) / h - 1.0)
+        if order == 3:
+            r1 = (self.lambda_t[s1] - lambda_b) / h
+            c['ir1'] = 1.0 / r1
+            if heun:
+                c.update(r0=r0, r1=r1, dr=r0 - r1)
+                if plus:
+                    c['k2'] = alpha_t * ((exp(-h) - 1.0 + h) / h ** 2 - 0.5)
+                else:
+                    c['k2'] = sigma_t * ((exp(h) - 1.0 - h) / h ** 2 - 0.5)
+        return {k: float(v) for k, v in c.items()}
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        """:558-612.  The order is order_list's at this step's index (see the class); exactly one launch, two with thresholding on
+        the dpmsolver++ branch, nothing read back."""
+        ts, last, t, i, prev_t = self._begin_solver_step(model_output, timestep, sample)
+        order = self.order_list[i]
+        sample, model_output = sample.contiguous(), model_output.contiguous()
+        if order == 1:
+            self.sample = sample                                      # a reference: the step of order 2 / 3 restarts from it
+        elif self.sample is None or i < order - 1 or any(h is None for h in self.model_outputs[-(order - 1):]):
+            raise ValueError('step %d is of order %d, and the steps it completes have not been taken' % (i, order))
+        coef = self.step_coefs(order, t, prev_t, ts[i - 1] if order >= 2 else None, ts[i - 2] if order == 3 else None)
+        plus = self.config.algorithm_type == 'dpmsolver++'
+        hist = self.model_outputs
+        prev, m0 = ops.dpm_single_step(sample, model_output, coef, order=order, pred=ops.X0_PRED[self.config.prediction_type],
+                                       data_pred=plus, heun=self.config.solver_type == 'heun',
+                                       xs=self.sample if order >= 2 else None,
+                                       m1=hist[-1] if order >= 2 else None, m2=hist[-2] if order == 3 else None,
+                                       stats=self._stats(sample, model_output, coef) if plus and self.config.thresholding else None,
+                                       m0_out=self._oldest_buffer(sample))
+        self._push_output(m0)
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+
 class PNDMScheduler(_SchedulerBase):
     """scheduling_pndm.py:58-427, F-PNDM: twelve Runge-Kutta calls (step_prk) and then the linear multistep method (step_plms), or
     the multistep method alone (`skip_prk_steps`), for epsilon and `v_prediction` models.  The counter logic is the reference's, its

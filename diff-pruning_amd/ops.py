@@ -2600,6 +2600,93 @@ def dynamic_threshold(sample, ratio=0.995, max_value=1.0, out=None):
                    out=out)[0]
 
 
+DEIS_MAX_BLOCKS = 4096               # DP_DEIS_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, one float4 per lane, strided beyond
+DEIS_COEF = ('sa', 'sb', 'kx', 'k0', 'at', 'as0', 'c1', 'c2', 'c3')
+DPM_SINGLE_COEF = ('sa', 'sb', 'kx', 'k0', 'k1', 'k2', 'ir0', 'ir1', 'r0', 'r1', 'dr')
+
+
+def dpm_single_reads_x(order, pred, data_pred):
+    """Whether dp_dpm_single_step reads `x`: the update at order 1, the conversion unless the model's output is what is kept."""
+    return order == 1 or pred != (X0_PRED_SAMPLE if data_pred else X0_PRED_EPSILON)
+
+
+def _solver_step_args(what, x, xs, m, hist, stats, out, m0_out):
+    """The checks ops.deis_step and ops.dpm_single_step share; (B, n, out, m0_out).  `x` / `xs`: None where the step does not read
+    them; `hist`: the history entries the step reads, newest first."""
+    total = m.numel()
+    assert m.dtype == _f32 and m.is_contiguous() and total >= 1
+    for t in (x, xs):
+        assert t is None or (t.dtype == _f32 and t.is_contiguous() and t.numel() == total)
+    assert all(h is not None and h.dtype == _f32 and h.is_contiguous() and h.numel() == total for h in hist), what + ': history below the order'
+    B, n = (1, total)
+    if stats is not None:
+        B, n = _rows(m)
+        assert stats.dtype == _f32 and stats.is_contiguous() and tuple(stats.shape) == (B, 4)
+    if out is None:
+        out = torch.empty_like(m)
+    if m0_out is None:
+        m0_out = torch.empty_like(m)
+    for o in (out, m0_out):
+        assert o.dtype == _f32 and o.is_contiguous() and o.numel() == total
+    assert out.data_ptr() not in [m.data_ptr(), m0_out.data_ptr()] + [h.data_ptr() for h in hist]
+    assert m0_out.data_ptr() not in [t.data_ptr() for t in (x, xs, m) if t is not None] + [h.data_ptr() for h in hist[:-1]]
+    return B, n, out, m0_out
+
+
+def deis_step(x, m, coef, order=1, pred=X0_PRED_EPSILON, m1=None, m2=None, stats=None, out=None, m0_out=None):
+    """One step of the DEIS multistep scheduler (dp_deis_step, csrc/deis.hip) over fp32 data.  `coef`: the host's fp32 scalars by name
+    (DEIS_COEF; one an order does not read may be left out):
+    x0 = (x - sb m) / sa | m | sa x - sb m by `pred`; with `stats` (x0_abs_quantile's [B, 4] table; the data is then [B, ...])
+    x0 = clamp(x0, -s, s) / s with the image's s; m0 = (x - sa x0) / sb;
+    order 1: x' = kx x - k0 m0;  order 2: x' = at ((x / as0 + c1 m0) + c2 m1);  order 3: x' = at (((x / as0 + c1 m0) + c2 m1) + c3 m2).
+    `m1` / `m2`: the previous converted output and the one before it, read from order 2 / 3 on.  `out` may be `x`; `m0_out` may be the
+    oldest history buffer the step reads (m1 at order 2, m2 at order 3); no other buffer may be shared.  Returns (out, m0_out)."""
+    assert order in (1, 2, 3) and pred in (X0_PRED_EPSILON, X0_PRED_SAMPLE, X0_PRED_V)
+    assert x is not None
+    hist = [m1, m2][:order - 1]
+    B, n, out, m0_out = _solver_step_args('deis_step', x, None, m, hist, stats, out, m0_out)
+    unknown = set(coef) - set(DEIS_COEF)
+    assert not unknown, unknown
+    c = L.DeisCoef(**{k: float(v) for k, v in coef.items()})
+    h = [_p(t) for t in hist] + [None] * (2 - len(hist))
+    L.check(_lib().dp_deis_step(_p(x), _p(m), h[0], h[1], _p(stats), int(order), int(pred), C.byref(c), _p(out), _p(m0_out), B, n,
+                                _stream()), 'dp_deis_step')
+    return out, m0_out
+
+
+def dpm_single_step(x, m, coef, order=1, pred=X0_PRED_EPSILON, data_pred=True, heun=False, xs=None, m1=None, m2=None, stats=None,
+                    out=None, m0_out=None):
+    """One step of the singlestep DPM-Solver (dp_dpm_single_step, csrc/deis.hip) over fp32 data.  `coef`: the host's fp32 scalars by
+    name (DPM_SINGLE_COEF; one an order / solver type does not read may be left out).
+    data_pred (dpmsolver++): m0 = x0 = (x - sb m) / sa | m | sa x - sb m by `pred`, with `stats` (x0_abs_quantile's [B, 4] table; the
+    data is then [B, ...]) clamp(x0, -s, s) / s;  not data_pred (dpmsolver, no stats): m0 = m | (x - sa m) / sb | sa m + sb x.
+    order 1: x' = kx x - k0 m0;  order 2: D1 = ir0 (m0 - m1), x' = (kx xs - k0 m1) - k1 D1;
+    order 3: D1_0 = ir1 (m1 - m2), D1_1 = ir0 (m0 - m2), midpoint: x' = (kx xs - k0 m2) - k1 D1_1,
+    `heun`: D1 = (r0 D1_0 - r1 D1_1) / dr, D2 = (2 (D1_1 - D1_0)) / dr, x' = ((kx xs - k0 m2) - k1 D1) - k2 D2.
+    `xs`: the saved sample of the order-1 step this one completes, read above order 1; `x` is not read (and may be None) where
+    dpm_single_reads_x says so.  `out` may be `x` or `xs`; `m0_out` may be the oldest history buffer the step reads (m1 at order 2,
+    m2 at order 3); no other buffer may be shared.  Returns (out, m0_out)."""
+    assert order in (1, 2, 3) and pred in (X0_PRED_EPSILON, X0_PRED_SAMPLE, X0_PRED_V)
+    assert stats is None or data_pred, 'dpm_single_step: the dpmsolver branch is never thresholded'
+    if not dpm_single_reads_x(order, pred, data_pred):
+        x = None
+    else:
+        assert x is not None
+    if order == 1:
+        xs = None
+    else:
+        assert xs is not None
+    hist = [m1, m2][:order - 1]
+    B, n, out, m0_out = _solver_step_args('dpm_single_step', x, xs, m, hist, stats, out, m0_out)
+    unknown = set(coef) - set(DPM_SINGLE_COEF)
+    assert not unknown, unknown
+    c = L.DpmSingleCoef(**{k: float(v) for k, v in coef.items()})
+    h = [_p(t) for t in hist] + [None] * (2 - len(hist))
+    L.check(_lib().dp_dpm_single_step(_p(x), _p(xs), _p(m), h[0], h[1], _p(stats), int(order), int(pred), 1 if data_pred else 0,
+                                      1 if heun else 0, C.byref(c), _p(out), _p(m0_out), B, n, _stream()), 'dp_dpm_single_step')
+    return out, m0_out
+
+
 VAE_MAX_BLOCKS = 4096                # DP_VAE_MAX_BLOCKS (include/dp_hip.h): 256 lanes each, grid-stride beyond
 POSTERIOR_OUTPUTS = ('logvar', 'std', 'var', 'z', 'kl')
 

@@ -523,7 +523,7 @@ int dp_ddpm_step(const float* x, const float* eps, const float* vnoise, float sq
                  float c_xt, float sigma, int clip, float clip_range, float* out, long long n, void* stream);
 
 /* ---- The head / body / tail access rule of the elementwise step launchers below (dp_denoise_step, dp_cfg_denoise_step,
- * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_repaint_step, dp_repaint_undo, dp_sigma_step and its two companions, dp_kdpm2_step, dp_lms_step, dp_x0_step and its two companions; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
+ * dp_dpm_solver_step, dp_unipc_step, dp_pndm_step, dp_repaint_step, dp_repaint_undo, dp_sigma_step and its two companions, dp_kdpm2_step, dp_lms_step, dp_x0_step and its two companions, dp_deis_step, dp_dpm_single_step; csrc/dp_headtail_plan.h decides, csrc/dp_headtail.h loops).
  * When every pointer in use (a NULL or unread one does not count) shares one 4-byte-aligned phase modulo 16, a scalar head of
  * 0 .. 3 elements brings all of them to 16 bytes: the n4 = (n - head) / 4 groups after it take 16-byte accesses, the head and the
  * n - head - 4 n4 tail elements 4-byte ones.  Otherwise every access is 4 bytes (head = n).  Any n: long long indexing, one lane
@@ -838,6 +838,51 @@ int dp_x0_step(const float* x, const float* m, const float* z, const float* stat
 int dp_x0_threshold_step(const float* x, const float* m, const float* z, int mode, int pred, int reclip, const dp_x0_coef* coef,
                          long long lo, long long hi, float w, float max_value, float* prev, float* x0_out, float* stats,
                          long long B, long long n, void* stream);
+
+/* One step of the DEIS multistep scheduler and of the singlestep DPM-Solver (csrc/deis.hip; diffusers/schedulers/
+ * scheduling_deis_multistep.py:240-405 and scheduling_dpmsolver_singlestep.py:291-519) for epsilon, sample and v-prediction models,
+ * one pass, in the reference's operation order.  m: the model's output; sa, sb: alpha_t and sigma_t of the step's timestep.
+ *   x0 = DP_X0_PRED_EPSILON: (x - sb m) / sa;  _SAMPLE: m;  _V: sa x - sb m          (the x0 of dp_x0_abs_quantile, bit for bit)
+ *   stats != NULL: the data is [B, n] and x0 = clamp(x0, -s, s) / s with s = stats[4 b + 3], as dp_x0_abs_quantile wrote it;
+ *   stats == NULL: no treatment, and the data is B n flat elements.
+ * dp_deis_step keeps m0 = (x - sa x0) / sb -- always, for an epsilon model too (the reference converts there and back), and
+ *   order 1:  x' = kx x - k0 m0
+ *   order 2:  x' = at ((x / as0 + c1 m0) + c2 m1)
+ *   order 3:  x' = at (((x / as0 + c1 m0) + c2 m1) + c3 m2)
+ * dp_dpm_single_step keeps, data_pred (dpmsolver++): m0 = the treated x0;  !data_pred (dpmsolver; stats must be NULL):
+ *   _EPSILON: m0 = m;  _SAMPLE: m0 = (x - sa m) / sb;  _V: m0 = sa m + sb x.   The conversion reads this call's x, the update the
+ *   saved sample xs of the order-1 step this one completes (x itself at order 1):
+ *   order 1:  x' = kx x - k0 m0
+ *   order 2:  D1 = ir0 (m0 - m1);                                              x' = (kx xs - k0 m1) - k1 D1
+ *   order 3:  D1_0 = ir1 (m1 - m2); D1_1 = ir0 (m0 - m2);           midpoint:  x' = (kx xs - k0 m2) - k1 D1_1
+ *             heun: D1 = (r0 D1_0 - r1 D1_1) / dr; D2 = (2 (D1_1 - D1_0)) / dr; x' = ((kx xs - k0 m2) - k1 D1) - k2 D2
+ * every operation rounded separately, true divisions; the scalars are the host's 0-d fp32 arithmetic (ir0 = 1 / r0, ir1 = 1 / r1,
+ * dr = r0 - r1); where the reference ADDS c * D1 the host passes k1 = -c, which gives the same bits.  Fields an order does not read
+ * are ignored.  m1 (the previous converted output) and m2 (the one before) may be NULL below their order; an input the step does
+ * not read is not loaded and may be NULL: xs at order 1, and above order 1 x for an epsilon model under dpmsolver or a sample
+ * model under dpmsolver++.  m0_out is always written.
+ * Aliases: `x_next` may be `x` itself (dp_dpm_single_step: or `xs` itself), and `m0_out` may be the oldest history buffer the step
+ * reads (m1 at order 2, m2 at order 3): each lane reads every input of its elements before it writes any of them, and no other lane
+ * touches them.  Any other overlap between an output and another buffer (stats included) is hipErrorInvalidValue, as are a null
+ * required pointer and an order outside 1 .. 3; B <= 0 or n <= 0 is a no-op.
+ * Accesses: the head / body / tail rule above -- with stats within every row when n % 4 == 0 (then every row has the first one's
+ * phase), 4-byte accesses otherwise; at most DP_DEIS_MAX_BLOCKS blocks of 256 lanes, strided over rows and images beyond. */
+#define DP_DEIS_MAX_BLOCKS 4096
+typedef struct dp_deis_coef {
+    float sa, sb;                       /* convert */
+    float kx, k0;                       /* order 1 */
+    float at, as0, c1, c2, c3;          /* orders 2 and 3 */
+} dp_deis_coef;
+typedef struct dp_dpm_single_coef {
+    float sa, sb;                       /* convert */
+    float kx, k0, k1, k2;               /* the update's coefficients */
+    float ir0, ir1, r0, r1, dr;         /* the difference quotients of orders 2 and 3 */
+} dp_dpm_single_coef;
+int dp_deis_step(const float* x, const float* m, const float* m1, const float* m2, const float* stats, int order, int pred,
+                 const dp_deis_coef* coef, float* x_next, float* m0_out, long long B, long long n, void* stream);
+int dp_dpm_single_step(const float* x, const float* xs, const float* m, const float* m1, const float* m2, const float* stats,
+                       int order, int pred, int data_pred, int heun, const dp_dpm_single_coef* coef, float* x_next, float* m0_out,
+                       long long B, long long n, void* stream);
 
 /* ---- LDM (CompVis) transformer-block glue on channel-major tokens x[n][c][t]  (ldm_exp/ldm/modules/attention.py) ---- */
 /* LayerNorm over the C channels of every token (attention.py:200-212 norm1/2/3); stats[(n*T+t)*2+{0,1}] = {mean, rstd}. */
